@@ -11,13 +11,19 @@ used by the cpu_baseline leg only, the parity tests proper are tests/ -m gpu). E
 data-path collective, so scaling is weak and torch.distributed is only used for
 the barrier and the max-over-ranks of the elapsed time.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up with W steps,
+times exactly K steps (a step is a fixed amount of work, --inner pairs; `ms_per_step` is one of them), writes the outputs of
+the last timed step if --dump-outputs is given, and prints the line. The round-trip and DFT checks named above, the further
+windows and everything below run with --full only.
+
 Also reported in the same JSON line:
   roofline      HBM roofline of the forward batch transform (the two ntt_pass_kernel launches),
                 algorithmic bytes = 16 B x 2^20 x 64 per batch transform,
-                duration from HIP events on the launch stream.
-  cpu_baseline  the C oracle (a restatement of the reference's fft_classic, "port") on this
+                duration from HIP events on the launch stream (--full adds the figures that take
+                runs of their own: pairs bracketed one by one, a copy kernel's bandwidth).
+  cpu_baseline  (--full) the C oracle (a restatement of the reference's fft_classic, "port") on this
                 host's cores, bounded sample.
-  extra         PolynomialBatch::from_values on BASELINE configs[2] (2^20 rows x 135 columns,
+  extra         (--full) PolynomialBatch::from_values on BASELINE configs[2] (2^20 rows x 135 columns,
                 rate 8, cap 4): ms per commit and Merkle leaves hashed/s (skipped with --no-commit);
                 prove() wall-clock on a synthetic circuit of configs[3]'s shape (n = 2^18, 234 wires,
                 88 preprocessed polynomials, FRI as standard_recursion_config), one independent proof
@@ -38,25 +44,34 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); what a copy kernel reaches is measured in the run
 LOG_N = 20
 BATCH = 64
-MIN_REGION_S = 0.5  # the timed region lasts at least this long (28 ms windows on devices that differ by 9 %)
+MIN_REGION_S = 0.5  # --inner 0: the timed region lasts at least this long (28 ms windows on devices that differ by 9 %)
+PAIRS_PER_STEP = 25  # what --inner 0 chose at the default 20 steps (profiles/r06_bench.json): 20 steps = a region of about 0.5 s
 WINDOWS = 5         # further windows of the same size after the timed one: median / min / max are reported beside `value`
+DUMP_SAMPLE = 1 << 20  # elements per dumped array: a fixed, seeded sample of the batch (16 MiB as float32 limbs)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--inner", type=int, default=0, help="forward + inverse pairs per step (0 = as many as make the timed region >= 0.5 s)")
-    ap.add_argument("--windows", type=int, default=WINDOWS, help="repeats of the timed region reported as value_windows")
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--inner", type=int, default=PAIRS_PER_STEP,
+                    help="forward + inverse pairs of the batch per step (0 = as many as make the timed region >= 0.5 s at this --steps, "
+                         "from a short calibration: the step then depends on --steps and on the device)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the parity checks, the further windows, the roofline figures that take runs "
+                         "of their own, the commit and prove legs, the CPU baselines and the reference's kernels (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--windows", type=int, default=WINDOWS, help="with --full: repeats of the timed region reported as value_windows")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-commit", action="store_true", help="skip the configs[2] commit measurement")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-prove", action="store_true", help="skip the configs[3]/[4]-shaped prove() measurement")
-    ap.add_argument("--no-reference", action="store_true", help="skip timing the reference's own kernels (oracle/_ref) on this GPU")
+    ap.add_argument("--no-commit", action="store_true", help="with --full: skip the configs[2] commit measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-prove", action="store_true", help="with --full: skip the configs[3]/[4]-shaped prove() measurement")
+    ap.add_argument("--no-reference", action="store_true", help="with --full: skip timing the reference's own kernels (oracle/_ref) on this GPU")
     ap.add_argument("--dry-ranks", action="store_true",
-                    help="N > 1 ranks on whatever devices there are, over a HOST backend, through the code the RCCL route takes (device tensors over the "
+                    help="with --full: N > 1 ranks on whatever devices there are, over a HOST backend, through the code the RCCL route takes (device tensors over the "
                          "library's pointers, staged through host memory for transport only), with the invariants of the N-rank line checked: see dry_ranks_checks")
     ap.add_argument("--reference-leg-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--prove-degree-bits", type=int, default=18)
@@ -322,6 +337,34 @@ def dft_point(x, log_n, k):
     return int(terms[0])
 
 
+def field_limbs_f32(a):
+    """u64 field elements -> float32 [..., 4]: their four 16-bit limbs, least significant first (exact in float32)."""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([((a >> np.uint64(16 * i)) & np.uint64(0xFFFF)).astype(np.float32) for i in range(4)], axis=-1)
+
+
+def dump_outputs(out_dir, _lib, ctx, buf, batch, log_n):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of gl_ntt_batch receives it, for comparing two
+    builds output for output (the inputs depend on the arguments only). A step transforms the batch forward and back in place:
+      ntt_batch_after_last_step.npy  the batch as the last timed step left it (the inverse transform's output);
+      ntt_forward_of_batch.npy       the forward transform of that batch — the forward output of the step's pairs
+                                     (computed here once more, outside the timed region, then transformed back).
+    Each holds the same fixed, seeded sample of DUMP_SAMPLE positions of the [batch][2^log_n] array (all of it when smaller), in
+    row-major order, as float32 [DUMP_SAMPLE, 4]: the four 16-bit limbs of each element, least significant first."""
+    n = 1 << log_n
+    total = batch * n
+    idx = np.arange(total) if total <= DUMP_SAMPLE else np.sort(np.random.default_rng(SPLITMIX_SEED).integers(0, total, size=DUMP_SAMPLE))
+    ctx.synchronize()
+    after = buf.download()[idx]
+    _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 0, 0, ctx.ptr)
+    forward = buf.download()[idx]
+    _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 1, 0, ctx.ptr)
+    ctx.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ntt_batch_after_last_step.npy"), field_limbs_f32(after))
+    np.save(os.path.join(out_dir, "ntt_forward_of_batch.npy"), field_limbs_f32(forward))
+
+
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r06_pmc_summary.json")  # tools/pmc_summary.py over the rocprofv3 --pmc passes
 # the kernel sources whose counters the summary holds: tools/pmc_summary.py records their sha256 next to the counters
 PMC_SOURCES = ["plonky2_gpu_amd/csrc/ntt.hip", "plonky2_gpu_amd/csrc/ntt_direct.hip", "plonky2_gpu_amd/csrc/ntt_kernels.h",
@@ -504,6 +547,10 @@ def main():
         return cpu_baseline_reference_leg_child(args)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dry_ranks and not args.full:
+        raise SystemExit("bench.py: --dry-ranks checks the legs of --full: add --full")
+    if not args.full:  # a plain run times the headline alone: every leg after it belongs to --full
+        args.no_commit = args.no_prove = args.no_cpu = args.no_reference = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # nothing below has run yet: no HIP call in this process
     import plonky2_gpu_amd as pg
@@ -544,18 +591,20 @@ def main():
         _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 0, 0, ctx.ptr)
         _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 1, 0, ctx.ptr)
 
-    # A step is `inner` forward + inverse transforms of the batch. One pair takes about 1.2 ms, and devices of the pool differ
-    # by several per cent on the same binary, so the timed region is kept at >= MIN_REGION_S whatever --steps says: `inner`
-    # is set from a short calibration (the same on every rank: max over ranks) and printed in config.
-    for _ in range(3):
-        pair()
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(8):
-        pair()
-    ctx.synchronize()
-    t_pair = dist.max((time.perf_counter() - t0) / 8)
-    inner = args.inner if args.inner > 0 else max(1, int(np.ceil(1.15 * MIN_REGION_S / (args.steps * t_pair))))  # 15 % margin: the calibration pairs run on a cold clock
+    # A step is `inner` forward + inverse transforms of the batch (PAIRS_PER_STEP by default: a fixed amount of work, so that
+    # `ms_per_step` says what a step costs at any --steps). With --inner 0 the timed region is kept at >= MIN_REGION_S whatever
+    # --steps says: `inner` is set from a short calibration (the same on every rank: max over ranks). Printed in config.
+    inner = args.inner
+    if inner <= 0:
+        for _ in range(3):
+            pair()
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(8):
+            pair()
+        ctx.synchronize()
+        t_pair = dist.max((time.perf_counter() - t0) / 8)
+        inner = max(1, int(np.ceil(1.15 * MIN_REGION_S / (args.steps * t_pair))))  # 15 % margin: the calibration pairs run on a cold clock
 
     def step():
         for _ in range(inner):
@@ -580,55 +629,59 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed = timed_window()  # THE timed region: exactly --steps steps between barrier + synchronize on both sides
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, _lib, ctx, buf, batch, log_n)
     # the same region again, WINDOWS times: the spread says how much one window can be trusted
-    window_s = [elapsed] + [timed_window() for _ in range(max(0, args.windows))]
+    window_s = [elapsed] + ([timed_window() for _ in range(max(0, args.windows))] if args.full else [])
 
-    # parity: after an equal number of forward/inverse transforms the batch must equal the input
-    back = buf.download().reshape(batch, n)
-    if not (back == host).all():
-        raise SystemExit("bench: ifft(fft(x)) != x — results invalid")
+    if args.full:
+        # parity: after an equal number of forward/inverse transforms the batch must equal the input
+        back = buf.download().reshape(batch, n)
+        if not (back == host).all():
+            raise SystemExit("bench: ifft(fft(x)) != x — results invalid")
 
     # The roofline's kernel = one batch transform = one launch pair (column pass + row pass; the forward and the inverse instance
     # alternate in the timed region and differ by the inverse's index flip in the row pass's stores). Its average launch duration
     # = the timed region between two HIP events on the launch stream / the launch pairs in it: what `rocprofv3 --kernel-trace
-    # --stats` of this command reports for the two kernels together (profiles/). Bracketing every pair with its own events is
-    # kept beside it: each event is a marker the queue drains for, so those figures run 3-6 % higher.
+    # --stats` of this command reports for the two kernels together (profiles/). With --full, bracketing every pair with its own
+    # events is kept beside it: each event is a marker the queue drains for, so those figures run 3-6 % higher.
     launches_in_region = 2 * inner * args.steps
     pair_ms = region_events_ms[0] / launches_in_region
-    reps = max(40, args.steps)
-    ev = [pg.Event() for _ in range(2 * reps)]
-    fwd_ms = []
-    for r in range(reps):
-        ev[2 * r].record(ctx)
-        _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 0, 0, ctx.ptr)
-        ev[2 * r + 1].record(ctx)
-        _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 1, 0, ctx.ptr)
-    ctx.synchronize()
-    for r in range(reps):
-        fwd_ms.append(ev[2 * r + 1].elapsed_ms_since(ev[2 * r]))
-    fwd = float(np.median(fwd_ms))
     alg_bytes = 16.0 * n * batch
     achieved = alg_bytes / (pair_ms * 1e-3) / 1e9
-    # what a streaming kernel moves on this very device: a 16 B/lane copy of the same 512 MiB, read + write
-    scratch = pg.DeviceBuffer(ctx, batch * n)
-    cev = [pg.Event() for _ in range(2)]
-    copy_ms = []
-    for r in range(6):
-        cev[0].record(ctx)
-        _lib.call("gl_debug_copy", scratch.ptr, buf.ptr, 8 * batch * n, ctx.ptr)
-        cev[1].record(ctx)
+    if args.full:
+        reps = max(40, args.steps)
+        ev = [pg.Event() for _ in range(2 * reps)]
+        fwd_ms = []
+        for r in range(reps):
+            ev[2 * r].record(ctx)
+            _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 0, 0, ctx.ptr)
+            ev[2 * r + 1].record(ctx)
+            _lib.call("gl_ntt_batch", buf.ptr, batch, log_n, n, 1, 0, ctx.ptr)
         ctx.synchronize()
-        if r:
-            copy_ms.append(cev[1].elapsed_ms_since(cev[0]))
-    scratch.free()
-    copy_gbs = 2 * 8.0 * batch * n / (min(copy_ms) * 1e-3) / 1e9
+        for r in range(reps):
+            fwd_ms.append(ev[2 * r + 1].elapsed_ms_since(ev[2 * r]))
+        fwd = float(np.median(fwd_ms))
+        # what a streaming kernel moves on this very device: a 16 B/lane copy of the same 512 MiB, read + write
+        scratch = pg.DeviceBuffer(ctx, batch * n)
+        cev = [pg.Event() for _ in range(2)]
+        copy_ms = []
+        for r in range(6):
+            cev[0].record(ctx)
+            _lib.call("gl_debug_copy", scratch.ptr, buf.ptr, 8 * batch * n, ctx.ptr)
+            cev[1].record(ctx)
+            ctx.synchronize()
+            if r:
+                copy_ms.append(cev[1].elapsed_ms_since(cev[0]))
+        scratch.free()
+        copy_gbs = 2 * 8.0 * batch * n / (min(copy_ms) * 1e-3) / 1e9
     mulmods = (n // 2) * log_n * batch  # (N/2) lg N butterflies per transform, one mulmod + add + sub each
     traffic, traffic_source = pmc_traffic(log_n, batch)
     _d, _ = pmc_summary()
     int_alu = int_alu_of_summary(_d) if (_d and log_n == 20) else None
 
     out = None
-    if dist.rank == 0:
+    if dist.rank == 0 and args.full:
         # Outside the timed region, and without the oracle (which only the cpu_baseline leg may touch): the
         # forward transform of column 0 against the DEFINITION X[k] = sum_j x[j] w^(jk) at a few output
         # indices, evaluated with vectorised numpy field arithmetic. With the round trip above this pins the
@@ -694,7 +747,7 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "value_windows": {"count": len(rates), "median": rates[len(rates) // 2], "min": rates[0], "max": rates[-1],
                               "seconds_per_window": round(float(np.median(window_s)), 3),
-                              "note": "the timed region (`value`) and WINDOWS repeats of it, NTT/s each"},
+                              "note": "the timed region (`value`) and, with --full, WINDOWS repeats of it, NTT/s each"},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -734,10 +787,6 @@ def main():
                 "ms_definition": "HIP events around the timed region on the launch stream / launch pairs in it",
                 "ms_launch_pairs_timed": launches_in_region,
                 "ms_all_windows": [w / launches_in_region for w in region_events_ms],
-                "ms_forward_pairs_bracketed_one_by_one": {"median": fwd, "min": float(min(fwd_ms)), "max": float(max(fwd_ms)), "pairs": reps,
-                                                          "note": "every event is a marker the queue drains for: 3-6 % above the region's average"},
-                "measured_copy_GBps": copy_gbs,
-                "frac_of_measured_copy": achieved / copy_gbs,
                 "algorithmic_butterflies_per_launch_pair": mulmods,
                 "butterflies_per_s": mulmods / (pair_ms * 1e-3),
             },
@@ -745,6 +794,13 @@ def main():
             "cpu_baseline": None if (args.no_cpu or dist.world > 1) else guarded_leg("cpu_baseline", lambda: cpu_baseline(log_n), {"value": None, "unit": "NTT/s", "cores": None, "kind": "port"}),
             "extra": extra,
         }
+        if args.full:
+            out["roofline"].update({
+                "ms_forward_pairs_bracketed_one_by_one": {"median": fwd, "min": float(min(fwd_ms)), "max": float(max(fwd_ms)), "pairs": reps,
+                                                          "note": "every event is a marker the queue drains for: 3-6 % above the region's average"},
+                "measured_copy_GBps": copy_gbs,
+                "frac_of_measured_copy": achieved / copy_gbs,
+            })
         if not (args.no_cpu or dist.world > 1):
             # The other two legs of the metric on this host's cores, and the reference's own kernels on this GPU. Each leg is guarded:
             # a CPU leg that fails (no compiler for the oracle, out of host memory) costs that leg, never the GPU measurements above.

@@ -57,7 +57,7 @@ def test_bench_with_two_ranks_prints_one_line_for_the_whole_job(gpu, launcher):
     import json
 
     bench = os.path.join(ROOT, "bench.py")
-    tail = [bench, "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    tail = [bench, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(29500 + os.getpid() % 400)] + tail
@@ -114,7 +114,7 @@ def test_bench_on_two_devices_synchronises_over_rccl(gpu):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-commit"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-commit"], env=env,
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -123,7 +123,7 @@ def test_bench_on_two_devices_synchronises_over_rccl(gpu):
     assert len(pr["proofs_per_s_per_rank"]) == 2 and len(pr["wires_cap0_per_rank"]) == 2
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 4])  # N ranks + this process hold the one device at once: kept to at most five
 def test_dry_ranks_line_holds_its_invariants(gpu, world):
     """`bench.py --gpus N --dry-ranks`: N ranks on the one device there is, over gloo, through the code a node with
     a device per rank runs except for the backend string — the ranks are started by bench.py itself before anything touches the GPU,
@@ -137,7 +137,7 @@ def test_dry_ranks_line_holds_its_invariants(gpu, world):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PLONKY2_DIST_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dry-ranks", "--steps", "2", "--warmup", "1", "--batch", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dry-ranks", "--full", "--steps", "2", "--warmup", "1", "--batch", "8",
            "--log-n", "16", "--windows", "0", "--commit-cols", "40", "--commit-log-n", "12", "--prove-degree-bits", "12", "--prove-reps", "2",
            "--prove-in-flight", "0", "--prove-larger", ""]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
