@@ -14,7 +14,10 @@
  * Conventions
  *   - Field elements are plain-domain Goldilocks u64 (p = 2^64 - 2^32 + 1). Inputs may be any
  *     u64 representative (field/src/goldilocks_field.rs:26); every OUTPUT buffer holds canonical
- *     values (< p), i.e. exactly what the reference yields after `to_canonical_u64`.
+ *     values (< p), i.e. exactly what the reference yields after `to_canonical_u64`. Except for
+ *     gl_transpose, gl_ext2_interleave, gl_pack_leaf_ranges and the opened leaves of
+ *     gl_merkle_open_batch / gl_merkle_open_batch_device: pure data movement, the output holds the
+ *     input's words unchanged — canonical in, canonical out.
  *   - All `d_*` pointers are DEVICE pointers. The callee allocates nothing for data: the caller
  *     owns every buffer (as in the reference, plonky2/src/fri/oracle.rs:94-106). The library keeps,
  *     per device, a few hundred KiB of read-only twiddle tables, and per CONTEXT one workspace of
@@ -395,8 +398,9 @@ GlError gl_pack_leaf_ranges(const uint64_t *d_lde, uint64_t col_stride, uint32_t
 /* PolynomialBatch::from_coeffs (plonky2/src/fri/oracle.rs:911-977) without the host-side struct:
  *   d_coeffs   [poly_num][2^log_n]            in
  *   d_lde      [(poly_num+salt_size)][n_ext]  out, column-major, bit-reversed (n_ext = 2^(log_n+rate_bits));
- *              the salt_size trailing columns are read as given (caller-provided randomness,
- *              oracle.rs:998-1002) and take part in the leaf hash. They are read by kernels on a stream of the library's own
+ *              the salt_size trailing columns are the caller's input (caller-provided randomness,
+ *              oracle.rs:998-1002), any representative: they are reduced in place, so that d_lde and d_leaves
+ *              hold canonical words, and take part in the leaf hash. They are read by kernels on a stream of the library's own
  *              that starts behind everything queued on ctx's stream at the time of the call: write them on ctx's stream
  *              (gl_memcpy_*, a kernel launched there) or complete the writes before calling.
  *   d_leaves   [n_ext][poly_num+salt_size]    out, leaf-major (= merkle_tree.leaves); may be NULL. MAY overlap d_coeffs (the

@@ -477,6 +477,13 @@ hipError_t get_hash_stream(void *ctx, hipStream_t *hs, std::vector<hipEvent_t> *
     return hipSuccess;
 }
 
+// The caller's salt columns in d_lde, reduced in place: the tree hashes any representative alike, but d_lde and the leaf-major
+// copies of it (fused row stores, transpositions) are outputs and hold canonical words
+// (tests/test_gpu_representatives.py::test_commit_from_values_and_coeffs, lifted salts with leaf_major).
+__global__ __launch_bounds__(256) void canon_in_place_kernel(uint64_t *a, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) a[i] = gl::canon(a[i]);
+}
+
 GlError commit_from_coeffs_impl(const uint64_t *d_coeffs, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
                                 uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
                                 uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, Streams *s,
@@ -492,6 +499,12 @@ GlError commit_from_coeffs_impl(const uint64_t *d_coeffs, uint64_t poly_num, uin
     HIP_TRY(get_coset_tables(log_n, rate_bits, shift, s->stream, &ct));
     (void)sync_stream2_before_leaves;
     const uint32_t leaf_len = (uint32_t)(poly_num + salt_size);
+    if (salt_size) {  // on the caller's stream, ahead of everything below that reads the salt columns (the hash stream starts behind it)
+        const uint64_t words = (uint64_t)salt_size * n_ext, blocks = (words + 255) / 256;
+        hipLaunchKernelGGL(canon_in_place_kernel, dim3((unsigned)std::min<uint64_t>(blocks, 8192)), dim3(256), 0, s->stream,
+                           d_lde + poly_num * n_ext, words);
+        HIP_TRY(hipGetLastError());
+    }
     uint64_t CHUNK = 16;  // columns per pipeline step: two rate blocks
     if (const char *e = PLONKY2_KNOB("PLONKY2_COMMIT_CHUNK")) {  // diagnostic build: another multiple of 8
         const unsigned long v = strtoul(e, nullptr, 10);
