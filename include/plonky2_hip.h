@@ -130,7 +130,10 @@ void gl_event_destroy(void *event);
  *   inverse = 1: ifft_with_options                        (field/src/fft.rs:73-103)
  *   bit_reversed = 1 (forward only): output slot m holds the value of natural index bitrev(m),
  *     i.e. reverse_index_bits(fft(x)) (util/src/lib.rs:188) — the Merkle leaf order.
- * log_n <= 24. For inverse, stride must be a multiple of 2^log_n. */
+ * log_n <= 24. stride >= 2^log_n; for inverse, stride must be a multiple of 2^log_n. The passes move 16 bytes at a time:
+ * d_values must be 16-byte aligned and, when poly_num > 1 and log_n > 0, stride even (one polynomial has no stride: any
+ * value >= 2^log_n is accepted). Words between the polynomials (stride > 2^log_n) are not written. A violation is
+ * GL_E_INVALID and nothing is touched. */
 GlError gl_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint64_t stride, int inverse,
                      int bit_reversed, void *ctx);
 
@@ -138,14 +141,19 @@ GlError gl_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint
  * 2^(log_n+rate_bits) evaluations on shift*H, BIT-REVERSED order:
  *   d_out[i*dst_stride + m] = coset_fft_with_options(lde(coeffs_i, rate_bits), shift)[bitrev(m)]
  * (field/src/polynomial/mod.rs:205-207, 286-299; fri/oracle.rs:979-1004 then :942-952 per column).
- * d_out must not overlap d_coeffs. */
+ * d_out must not overlap d_coeffs. log_n <= 24, rate_bits <= 8. src_stride >= 2^log_n and dst_stride >= 2^(log_n+rate_bits), both
+ * even when log_n > 0 (for any poly_num), both buffers 16-byte aligned; a violation is GL_E_INVALID. Any such dst_stride works at
+ * every size (a padded column pitch for the LDE buffer); at log_n >= 22 (three passes) a dst_stride other than
+ * 2^(log_n+rate_bits) runs the polynomials one launch sequence at a time. Words between the columns are not written. */
 GlError gl_coset_lde_batch(const uint64_t *d_coeffs, uint64_t *d_out, uint64_t poly_num, uint32_t log_n,
                            uint32_t rate_bits, uint64_t shift, uint64_t src_stride, uint64_t dst_stride, void *ctx);
 
 /* Natural-order coset transforms, in place:
  *   inverse = 0: PolynomialCoeffs::coset_fft(shift)   (field/src/polynomial/mod.rs:281-299)
  *   inverse = 1: PolynomialValues::coset_ifft(shift)  (field/src/polynomial/mod.rs:64-77) — the
- *               last step of compute_quotient_polys (plonk/prover.rs:1009-1021). */
+ *               last step of compute_quotient_polys (plonk/prover.rs:1009-1021).
+ * d_values, log_n and stride obey the rules of gl_ntt_batch (alignment, even stride, inverse: stride % 2^log_n == 0); they are
+ * checked before anything is scaled: a refused call (GL_E_INVALID) leaves d_values as it was. */
 GlError gl_coset_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint64_t stride, uint64_t shift, int inverse,
                            void *ctx);
 
@@ -274,7 +282,9 @@ typedef struct GlQuotientArgs {
     const GlGateProgram *gate_program; /* HOST struct, may be NULL; exclusive with d_gate_constraint_terms */
     /* 0: the three d_*_leaves are leaf-major rows [n_ext][leaf_len] (d_leaves of gl_commit_*);
      * otherwise they are the column-major LDE [leaf_len][column_stride] in bit-reversed row order
-     * (d_lde of gl_commit_*) — coalesced reads, and no leaf-major copy has to exist at all. */
+     * (d_lde of gl_commit_*) — coalesced reads, and no leaf-major copy has to exist at all. Any value
+     * >= 2^degree_bits << log2_ceil(quotient_degree_factor), the rows the kernel reads, is a legal column pitch (the padded
+     * pitch of gl_coset_lde_batch's dst_stride); a smaller non-zero one is GL_E_INVALID. */
     uint64_t column_stride;
     /* Gates compiled by gl_gate_kernel_build (may be NULL; exclusive with the two other sources of gate
      * constraints). Needs h_public_inputs_hash (4, host) and d_gate_workspace
@@ -361,7 +371,7 @@ GlError gl_challenger_step(uint64_t *d_challenger, const GlObserveSrc *h_srcs, u
 /* MerkleTree::prove (plonky2/src/hash/merkle_tree.rs:392-440) and the leaf itself for `count` leaf
  * indices in one launch and one copy — what fri_prover_query_round (fri/prover.rs:199-260) does per
  * query and tree. Element j of leaf i is read at d_leaves[i*row_stride + j*elem_stride] (leaf-major rows:
- * (leaf_len, 1); the LDE's columns: (1, n_leaves)). Host outputs: h_out_leaves[count][leaf_len],
+ * (leaf_len, 1); the LDE's columns: (1, col_stride), col_stride >= n_leaves the column pitch). Host outputs: h_out_leaves[count][leaf_len],
  * h_out_siblings[count][log2(n_leaves) - cap_height][4]. SYNCHRONOUS. */
 GlError gl_merkle_open_batch(const uint64_t *d_leaves, uint64_t row_stride, uint64_t elem_stride, uint32_t leaf_len, uint64_t n_leaves,
                              uint32_t cap_height, const uint64_t *d_digests, const uint64_t *h_indices, uint32_t count,
@@ -378,20 +388,24 @@ GlError gl_merkle_open_batch_device(const uint64_t *d_leaves, uint64_t row_strid
  *   _columns: d_cols[j*col_stride + i] = element j of leaf i   (the NTT's output layout)
  *   _leaves : d_rows[i*leaf_len + j]                            (the reference's Vec<Vec<F>>)
  * d_digests: 4*2*(n_leaves - 2^cap_height) u64, reference layout (merkle_tree.rs:46-54);
- * d_cap: 4*2^cap_height u64. cap_height > log2(n_leaves) -> GL_E_INVALID (the reference panics). */
+ * d_cap: 4*2^cap_height u64. cap_height > log2(n_leaves) -> GL_E_INVALID (the reference panics).
+ * col_stride >= n_leaves, odd or even (the columns are read word by word; d_cols 8-byte aligned); a smaller one would make the
+ * columns overlap: GL_E_INVALID. The one exception is leaf_len <= 1, where col_stride is not used and may be anything. */
 GlError gl_merkle_tree_from_columns(const uint64_t *d_cols, uint32_t leaf_len, uint64_t n_leaves, uint64_t col_stride,
                                     uint32_t cap_height, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
 GlError gl_merkle_tree_from_leaves(const uint64_t *d_rows, uint32_t leaf_len, uint64_t n_leaves, uint32_t cap_height,
                                    uint64_t *d_digests, uint64_t *d_cap, void *ctx);
 
-/* d_cols[c*col_stride + r] -> d_rows[r*n_cols + c]  (plonky2/src/util/mod.rs:23-53) */
+/* d_cols[c*col_stride + r] -> d_rows[r*n_cols + c]  (plonky2/src/util/mod.rs:23-53). col_stride >= n_rows, odd or even;
+ * a smaller one is GL_E_INVALID, except for n_cols <= 1, where it is not used. */
 GlError gl_transpose(const uint64_t *d_cols, uint64_t *d_rows, uint32_t n_cols, uint64_t n_rows, uint64_t col_stride,
                      void *ctx);
 
 /* The pack step of a commitment whose columns are sharded over `world` GPUs (one process per GPU; plonky2_gpu_amd/dist.py):
  * d_out[(q*n_cols + c)*leaves_per_rank + i] = d_lde[c*col_stride + q*leaves_per_rank + i] — for every rank q, the leaf
  * range it will hash of every one of this rank's n_cols LDE columns, contiguous per destination rank, in ONE launch
- * (d_out: world * n_cols * leaves_per_rank elements). The slices go out as they are with one send per peer. */
+ * (d_out: world * n_cols * leaves_per_rank elements). The slices go out as they are with one send per peer.
+ * leaves_per_rank and col_stride even, col_stride >= world * leaves_per_rank, both buffers 16-byte aligned (else GL_E_INVALID). */
 GlError gl_pack_leaf_ranges(const uint64_t *d_lde, uint64_t col_stride, uint32_t n_cols, uint64_t leaves_per_rank, uint32_t world,
                             uint64_t *d_out, void *ctx);
 

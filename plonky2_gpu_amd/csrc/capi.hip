@@ -784,20 +784,30 @@ void gl_event_destroy(void *event) {
     if (event) (void)hipEventDestroy((hipEvent_t)event);
 }
 
+// the argument rules of gl_ntt_batch (include/plonky2_hip.h), also checked by gl_coset_ntt_batch BEFORE it scales the values: a refused
+// call leaves the caller's buffer as it was
+static const char *ntt_batch_argument_error(const uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint64_t stride, int inverse,
+                                            int bit_reversed) {
+    if (log_n > 24) return "log_n > 24 is not supported by this build";
+    if (stride < (1ull << log_n)) return "stride smaller than the polynomial";
+    if (inverse && bit_reversed) return "bit-reversed inverse is not on the hot path";
+    if (inverse && (stride & ((1ull << log_n) - 1))) return "inverse needs stride % n == 0";
+    if ((stride & 1) && log_n > 0 && poly_num > 1) return "stride must be even (16-byte accesses)";
+    if ((uintptr_t)d_values & 15) return "d_values must be 16-byte aligned";
+    return nullptr;
+}
+
 GlError gl_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint64_t stride, int inverse,
                      int bit_reversed, void *ctx) {
     DeviceCall device_call(ctx);
     if (!ctx || (!d_values && poly_num)) return fail(GL_E_INVALID, "null pointer");
-    if (log_n > 24) return fail(GL_E_INVALID, "log_n > 24 is not supported by this build");
-    if (stride < (1ull << log_n)) return fail(GL_E_INVALID, "stride smaller than the polynomial");
-    if (inverse && bit_reversed) return fail(GL_E_INVALID, "bit-reversed inverse is not on the hot path");
-    if (inverse && (stride & ((1ull << log_n) - 1))) return fail(GL_E_INVALID, "inverse needs stride % n == 0");
-    if ((stride & 1) && log_n > 0 && poly_num > 1) return fail(GL_E_INVALID, "stride must be even (16-byte accesses)");
-    if ((uintptr_t)d_values & 15) return fail(GL_E_INVALID, "d_values must be 16-byte aligned");
+    if (const char *why = ntt_batch_argument_error(d_values, poly_num, log_n, stride, inverse, bit_reversed)) return fail(GL_E_INVALID, why);
     const NttTables *tb;
     HIP_TRY(get_tables(ctx, &tb));
-    HIP_TRY(ntt_batch(*tb, d_values, d_values, poly_num, log_n, stride, stride,
-                      bit_reversed ? NttOrder::BitReversed : NttOrder::Natural, inverse != 0, S(ctx)->stream));
+    hipError_t e = ntt_batch(*tb, d_values, d_values, poly_num, log_n, stride, stride,
+                             bit_reversed ? NttOrder::BitReversed : NttOrder::Natural, inverse != 0, S(ctx)->stream);
+    if (e == hipErrorInvalidValue) return fail(GL_E_INVALID, "gl_ntt_batch: size, order, stride or batch outside what the pass plans take");
+    HIP_TRY(e);
     return ok();
 }
 
@@ -814,7 +824,9 @@ GlError gl_coset_lde_batch(const uint64_t *d_coeffs, uint64_t *d_out, uint64_t p
     CosetLease ct;
     HIP_TRY(get_tables(ctx, &tb));
     HIP_TRY(get_coset_tables(log_n, rate_bits, shift, S(ctx)->stream, &ct));
-    HIP_TRY(coset_lde_batch(*tb, *ct, d_coeffs, d_out, poly_num, src_stride, dst_stride, S(ctx)->stream));
+    hipError_t e = coset_lde_batch(*tb, *ct, d_coeffs, d_out, poly_num, src_stride, dst_stride, S(ctx)->stream);
+    if (e == hipErrorInvalidValue) return fail(GL_E_INVALID, "gl_coset_lde_batch: size, strides or batch outside what the pass plans take");
+    HIP_TRY(e);
     return ok();
 }
 
@@ -823,6 +835,7 @@ GlError gl_coset_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n
     DeviceCall device_call(ctx);
     if (!ctx || (!d_values && poly_num)) return fail(GL_E_INVALID, "null pointer");
     if (shift % glh::P == 0) return fail(GL_E_INVALID, "shift must be non-zero");
+    if (const char *why = ntt_batch_argument_error(d_values, poly_num, log_n, stride, inverse, 0)) return fail(GL_E_INVALID, why);
     CosetLease ct;
     if (!inverse) {
         // coset_fft: c_i *= shift^i, then fft (polynomial/mod.rs:286-299)
@@ -928,6 +941,8 @@ GlError gl_compute_quotient_polys(const GlQuotientArgs *args, uint64_t *d_quotie
     while ((1u << qdb) < a.quotient_degree_factor) qdb++;
     if (a.quotient_degree_factor < 2 || qdb > a.rate_bits)
         return fail(GL_E_INVALID, "constraints of degree higher than the rate are not supported (prover.rs:807-811)");
+    if (a.column_stride && a.degree_bits + qdb <= 24 && a.column_stride < (1ull << (a.degree_bits + qdb)))
+        return fail(GL_E_INVALID, "column_stride smaller than the column length n << log2_ceil(quotient_degree_factor)");
     const NttTables *tb;
     HIP_TRY(get_tables(ctx, &tb));
     hipError_t e = quotient_values(*tb, a, d_quotient_polys, S(ctx)->stream);
@@ -1115,6 +1130,7 @@ GlError gl_merkle_tree_from_columns(const uint64_t *d_cols, uint32_t leaf_len, u
     if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return fail(GL_E_INVALID, "n_leaves must be a power of two");
     if ((1ull << cap_height) > n_leaves || cap_height > 63)
         return fail(GL_E_INVALID, "cap_height should be at most log2(leaves.len())");
+    if (leaf_len > 1 && col_stride < n_leaves) return fail(GL_E_INVALID, "col_stride smaller than n_leaves: the columns would overlap");
     HIP_TRY(merkle_tree_from_columns(d_cols, leaf_len, n_leaves, col_stride, cap_height, d_digests, d_cap, S(ctx)->stream));
     return ok();
 }
@@ -1134,6 +1150,7 @@ GlError gl_transpose(const uint64_t *d_cols, uint64_t *d_rows, uint32_t n_cols, 
                      void *ctx) {
     DeviceCall device_call(ctx);
     if (!ctx || !d_cols || !d_rows) return fail(GL_E_INVALID, "null pointer");
+    if (n_cols > 1 && col_stride < n_rows) return fail(GL_E_INVALID, "col_stride smaller than n_rows: the columns would overlap");
     HIP_TRY(transpose_to_leaf_major(d_cols, d_rows, n_cols, n_rows, col_stride, S(ctx)->stream));
     return ok();
 }

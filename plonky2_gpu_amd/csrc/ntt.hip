@@ -1256,8 +1256,16 @@ hipError_t coset_lde_batch(const NttTables &tb, const CosetTables &ct, const uin
         return hipSuccess;
     }
     if (log_n > 21 || (log_n == 21 && !wide_ok(11, 1024))) {
-        // three-pass sizes; needs the coset blocks of all polynomials contiguous (dst_stride = n << rate_bits)
-        if (dst_stride != n_cosets * n) return hipErrorInvalidValue;
+        // three-pass sizes; passes 2 and 3 enumerate (polynomial, coset block) as one index with stride n, so they need the coset
+        // blocks of all polynomials of a launch contiguous (dst_stride = n << rate_bits): with a padded dst_stride the polynomials
+        // go one call at a time, as in the small path above (a polynomial's own blocks are always contiguous)
+        if (dst_stride != n_cosets * n) {
+            for (uint64_t i = 0; i < n_polys; i++) {
+                hipError_t e = coset_lde_batch(tb, ct, coeffs + i * src_stride, dst + i * dst_stride, 1, src_stride, n_cosets * n, stream);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        }
         const uint32_t la = (log_n + 2) / 3, lb = (log_n - la + 1) / 2, lc = log_n - la - lb;
         const uint64_t N1 = 1ull << la, N2 = 1ull << lb, N3 = 1ull << lc, N23 = N2 * N3;
         const uint32_t logt1 = LOGE - la, T1 = 1u << logt1, logt2 = LOGE - lb, T2 = 1u << logt2, logt3 = LOGE - lc,

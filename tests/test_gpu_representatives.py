@@ -267,8 +267,8 @@ def _quotient(gpu, d_w, d_cs, d_z, leaf_lens, column_stride, inst, k_is, betas, 
 def test_compute_quotient_polys(gpu, num_ch):
     """all three leaf buffers lifted (selectors among them: the gate filter's sub(i, s) with s >= p is gl::sub's second borrow),
     k_is, alphas / betas / gammas, the gate terms and the public-inputs hash; every gate source (none: the fast kernels
-    <num_challenges>; a term array, the interpreter, the compiled kernel: the generic kernel), leaf-major and column-major,
-    the coset shift given as 7 + p"""
+    <num_challenges>; a term array, the interpreter, the compiled kernel: the generic kernel), leaf-major and column-major (at a
+    column stride of n_ext and at a padded one), the coset shift given as 7 + p"""
     import plonky2_gpu_amd as pg
     from oracle import plonk_ref, pyref
     from plonky2_gpu_amd import gate_program as gp
@@ -312,13 +312,14 @@ def test_compute_quotient_polys(gpu, num_ch):
            "program": plonk_ref.compute_quotient_polys(*ref_args, gate_terms)}
     exp["kernel"] = exp["program"]
     for source in ("none", "terms", "program", "kernel"):
-        for column_stride in (0, n_ext):
+        for column_stride in (0, n_ext, n_ext + 2):  # n_ext + 2: a padded column pitch, the pad words no field elements
             outs = []
             for key in ("canon", "lifted"):
                 lf = key == "lifted"
                 bufs = [lifted[nm] if lf else a for nm, a in (("w", w_l), ("cs", cs_l), ("z", z_l))]
                 if column_stride:
-                    bufs = [np.ascontiguousarray(a.T) for a in bufs]
+                    bufs = [np.concatenate([a.T, np.full((a.shape[1], column_stride - n_ext), 0xFFFFFFFFDEADBEEF, dtype=np.uint64)], axis=1)
+                            for a in bufs]
                 d = [_buf(gpu, a) for a in bufs]
                 d_t = _buf(gpu, lifted["terms"] if lf else terms)
                 outs.append(_quotient(gpu, d[0], d[1], d[2], (12, nc + 12, nz), column_stride, inst,
