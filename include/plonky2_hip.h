@@ -431,6 +431,40 @@ GlError gl_commit_from_values(uint64_t *d_values, uint64_t poly_num, uint32_t lo
                               uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
                               uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
 
+/* ---- Keccak Merkle trees and commits: plonky2's KeccakGoldilocksConfig (plonk/config.rs:110-128) -----------------
+ * The two GenericConfigs of plonky2 differ in the Hasher that builds Merkle trees only: PoseidonHash or KeccakHash<25>
+ * (hash/keccak.rs:53-83); field, extension, challenger and the public-input hash are the same. The `_h` entry points below
+ * are the un-suffixed ones with that hasher as their first argument; GL_HASHER_POSEIDON forwards to the un-suffixed call
+ * (same bytes out), an unknown value is GL_E_INVALID. With GL_HASHER_KECCAK25:
+ *   hash_no_pad(x)   = the first 25 bytes of Keccak-256 (original padding 0x01 .. 0x80, rate 136 bytes = 17 elements) of the
+ *                      canonical words of x, little endian (util/serialization.rs:492-509); inputs may be any u64
+ *                      representative, they are reduced before they are absorbed;
+ *   two_to_one(l, r) = the first 25 bytes of Keccak-256 of the 50 bytes l || r;
+ *   hash_or_noop(x)  = len <= 3: the canonical words, zero padded to 25 bytes; len >= 5: hash_no_pad; len == 4: the
+ *                      reference panics (a 32-byte slice of a 25-byte vector, plonk/config.rs:58-63): GL_E_INVALID, nothing written.
+ * DEVICE LAYOUT OF A DIGEST: a 32-byte slot (4 u64), bytes 0..24 the hash, bytes 25..31 zero. With that, every buffer size
+ * (d_digests: 4*2*(n_leaves - 2^cap_height) u64, d_cap: 4*2^cap_height u64), every digest index, gl_merkle_open_batch /
+ * gl_merkle_open_batch_device (siblings [count][layers][4], one slot each) and the region contract arithmetic are those of the
+ * Poseidon trees, unchanged. A host reads a hash as the first 25 bytes of its slot.
+ * The `_h` commits keep the whole contract of gl_commit_*: d_lde and d_leaves do not depend on the hasher, d_leaves may be NULL
+ * or overlap d_coeffs, salt columns are reduced in place and hashed, the caller's stream continues only after the tree (and the
+ * leaves), and a failing call leaves no work running on a stream other than the caller's own.
+ * Not covered: gl_circuit_create / gl_prove and the reference's seven symbols are Poseidon-only. */
+enum GlHasher { GL_HASHER_POSEIDON = 0, GL_HASHER_KECCAK25 = 1 };
+/* count inputs of len elements at d_inputs[i*stride ..), stride >= len when count > 1; d_out[count][4] in the slot layout above.
+ * d_out 16-byte aligned. Always hash_no_pad, whatever len (0 included: the hash of the empty message). */
+GlError gl_keccak_hash_no_pad_batch(const uint64_t *d_inputs, uint32_t len, uint64_t stride, uint64_t count, uint64_t *d_out, void *ctx);
+GlError gl_merkle_tree_from_columns_h(uint32_t hasher, const uint64_t *d_cols, uint32_t leaf_len, uint64_t n_leaves, uint64_t col_stride,
+                                      uint32_t cap_height, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
+GlError gl_merkle_tree_from_leaves_h(uint32_t hasher, const uint64_t *d_rows, uint32_t leaf_len, uint64_t n_leaves, uint32_t cap_height,
+                                     uint64_t *d_digests, uint64_t *d_cap, void *ctx);
+GlError gl_commit_from_coeffs_h(uint32_t hasher, const uint64_t *d_coeffs, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
+                                uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
+                                uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
+GlError gl_commit_from_values_h(uint32_t hasher, uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
+                                uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
+                                uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
+
 /* ---- the whole prover in two calls ---------------------------------------------------------------
  * gl_circuit_create = the prover-side part of CircuitBuilder::build (plonky2/src/plonk/circuit_builder.rs:
  * 849-960): uploads sigmas / k_is, commits constants||sigmas (constants_sigmas_commitment), derives the

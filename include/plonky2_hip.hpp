@@ -114,7 +114,17 @@ inline std::vector<uint64_t> ifft_with_options(const Context &ctx, const std::ve
     return d.download();
 }
 
-using HashOut = std::vector<uint64_t>;  // 4 elements (hash_types.rs:17-22)
+using HashOut = std::vector<uint64_t>;  // 4 elements (hash_types.rs:17-22); a Keccak hash: the first 25 bytes of the 4 words
+
+// The hasher of a Merkle tree: PoseidonGoldilocksConfig or KeccakGoldilocksConfig (plonk/config.rs:110-128).
+enum class Hasher : uint32_t { Poseidon = GL_HASHER_POSEIDON, Keccak = GL_HASHER_KECCAK25 };
+
+// BytesHash<25> of a digest slot (hash_types.rs:133-137): bytes 0..24 of its four little-endian words.
+inline std::vector<uint8_t> keccak_hash_bytes(const uint64_t *slot) {
+    std::vector<uint8_t> out(25);
+    for (int i = 0; i < 25; i++) out[i] = (uint8_t)(slot[i / 8] >> (8 * (i % 8)));
+    return out;
+}
 
 struct MerkleProof {
     std::vector<HashOut> siblings;  // merkle_proofs.rs:18-22
@@ -123,7 +133,9 @@ struct MerkleProof {
 class MerkleTree {
   public:
     // MerkleTree::new(leaves, cap_height) (merkle_tree.rs:283-319); leaves leaf-major [n_leaves][leaf_len].
-    static MerkleTree new_(const Context &ctx, const std::vector<uint64_t> &leaves, uint64_t n_leaves, uint32_t cap_height) {
+    // hasher: Poseidon (the default) or Keccak; the buffers, indices and prove() are the same for both.
+    static MerkleTree new_(const Context &ctx, const std::vector<uint64_t> &leaves, uint64_t n_leaves, uint32_t cap_height,
+                           Hasher hasher = Hasher::Poseidon) {
         uint32_t lg = log2_strict(n_leaves);
         if (cap_height > lg)
             throw Error(GL_E_INVALID, "cap_height=" + std::to_string(cap_height) + " should be at most log2(leaves.len())=" + std::to_string(lg));
@@ -135,14 +147,20 @@ class MerkleTree {
         t.d_leaves_ = DeviceBuffer(ctx, leaves);
         t.d_digests_ = DeviceBuffer(ctx, 8 * (n_leaves - (1ull << cap_height)) + 4);
         t.d_cap_ = DeviceBuffer(ctx, 4ull << cap_height);
-        check(gl_merkle_tree_from_leaves(t.d_leaves_.data(), t.leaf_len_, n_leaves, cap_height, t.d_digests_.data(),
-                                         t.d_cap_.data(), ctx.get()));
+        t.hasher_ = hasher;
+        if (hasher == Hasher::Poseidon)
+            check(gl_merkle_tree_from_leaves(t.d_leaves_.data(), t.leaf_len_, n_leaves, cap_height, t.d_digests_.data(),
+                                             t.d_cap_.data(), ctx.get()));
+        else
+            check(gl_merkle_tree_from_leaves_h((uint32_t)hasher, t.d_leaves_.data(), t.leaf_len_, n_leaves, cap_height, t.d_digests_.data(),
+                                               t.d_cap_.data(), ctx.get()));
         return t;
     }
     // adopt buffers produced by a commit
     static MerkleTree adopt(const Context &ctx, uint64_t n_leaves, uint32_t leaf_len, uint32_t cap_height, DeviceBuffer digests,
-                            DeviceBuffer cap, DeviceBuffer leaves) {
+                            DeviceBuffer cap, DeviceBuffer leaves, Hasher hasher = Hasher::Poseidon) {
         MerkleTree t;
+        t.hasher_ = hasher;
         t.ctx_ = &ctx; t.n_leaves_ = n_leaves; t.leaf_len_ = leaf_len; t.cap_height_ = cap_height;
         t.d_digests_ = std::move(digests); t.d_cap_ = std::move(cap); t.d_leaves_ = std::move(leaves);
         return t;
@@ -169,8 +187,10 @@ class MerkleTree {
     }
     uint64_t n_leaves() const { return n_leaves_; }
     uint32_t leaf_len() const { return leaf_len_; }
+    Hasher hasher() const { return hasher_; }
 
   private:
+    Hasher hasher_ = Hasher::Poseidon;
     const Context *ctx_ = nullptr;
     uint64_t n_leaves_ = 0;
     uint32_t leaf_len_ = 0, cap_height_ = 0;
@@ -184,13 +204,15 @@ class PolynomialBatch {
     // values: n_polys columns of length n, column-major. `salt` = SALT_SIZE columns of n<<rate_bits
     // elements when blinding (the reference draws them from OsRng, oracle.rs:998-1002).
     static PolynomialBatch from_values(const Context &ctx, const std::vector<uint64_t> &values, uint64_t n_polys, uint32_t rate_bits,
-                                       bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt = {}) {
-        return commit(ctx, values, n_polys, rate_bits, blinding, cap_height, salt, true);
+                                       bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt = {},
+                                       Hasher hasher = Hasher::Poseidon) {
+        return commit(ctx, values, n_polys, rate_bits, blinding, cap_height, salt, true, hasher);
     }
     // from_coeffs (oracle.rs:911-977)
     static PolynomialBatch from_coeffs(const Context &ctx, const std::vector<uint64_t> &coeffs, uint64_t n_polys, uint32_t rate_bits,
-                                       bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt = {}) {
-        return commit(ctx, coeffs, n_polys, rate_bits, blinding, cap_height, salt, false);
+                                       bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt = {},
+                                       Hasher hasher = Hasher::Poseidon) {
+        return commit(ctx, coeffs, n_polys, rate_bits, blinding, cap_height, salt, false, hasher);
     }
     std::vector<uint64_t> polynomials() const { return d_polys_.download(); }
     // get_lde_values(index, step) (oracle.rs:1007-1018)
@@ -207,7 +229,7 @@ class PolynomialBatch {
 
   private:
     static PolynomialBatch commit(const Context &ctx, const std::vector<uint64_t> &polys, uint64_t n_polys, uint32_t rate_bits,
-                                  bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt, bool is_values) {
+                                  bool blinding, uint32_t cap_height, const std::vector<uint64_t> &salt, bool is_values, Hasher hasher) {
         uint64_t n = polys.size() / n_polys;
         uint32_t lg = log2_strict(n);
         uint64_t n_ext = n << rate_bits;
@@ -221,16 +243,25 @@ class PolynomialBatch {
         b.d_lde_ = DeviceBuffer(ctx, cols * n_ext);
         if (salt_size) b.d_lde_.upload(salt, n_polys * n_ext);
         DeviceBuffer leaves(ctx, cols * n_ext), dig(ctx, 8 * (n_ext - (1ull << cap_height)) + 4), cap(ctx, 4ull << cap_height);
-        check((is_values ? gl_commit_from_values : gl_commit_from_coeffs_nc)(b.d_polys_.data(), n_polys, lg, rate_bits, cap_height, salt_size,
-                                                                              COSET_SHIFT, b.d_lde_.data(), leaves.data(), dig.data(),
-                                                                              cap.data(), ctx.get()));
+        if (hasher == Hasher::Poseidon)
+            check((is_values ? gl_commit_from_values : gl_commit_from_coeffs_nc)(b.d_polys_.data(), n_polys, lg, rate_bits, cap_height, salt_size,
+                                                                                  COSET_SHIFT, b.d_lde_.data(), leaves.data(), dig.data(),
+                                                                                  cap.data(), ctx.get()));
+        else
+            check((is_values ? gl_commit_from_values_h : gl_commit_from_coeffs_h_nc)((uint32_t)hasher, b.d_polys_.data(), n_polys, lg, rate_bits,
+                                                                                      cap_height, salt_size, COSET_SHIFT, b.d_lde_.data(),
+                                                                                      leaves.data(), dig.data(), cap.data(), ctx.get()));
         ctx.synchronize();
-        b.merkle_tree = MerkleTree::adopt(ctx, n_ext, (uint32_t)cols, cap_height, std::move(dig), std::move(cap), std::move(leaves));
+        b.merkle_tree = MerkleTree::adopt(ctx, n_ext, (uint32_t)cols, cap_height, std::move(dig), std::move(cap), std::move(leaves), hasher);
         return b;
     }
     static GlError gl_commit_from_coeffs_nc(uint64_t *c, uint64_t p, uint32_t l, uint32_t r, uint32_t h, uint32_t s, uint64_t sh, uint64_t *lde,
                                             uint64_t *lv, uint64_t *dg, uint64_t *cp, void *ctx) {
         return gl_commit_from_coeffs(c, p, l, r, h, s, sh, lde, lv, dg, cp, ctx);
+    }
+    static GlError gl_commit_from_coeffs_h_nc(uint32_t hs, uint64_t *c, uint64_t p, uint32_t l, uint32_t r, uint32_t h, uint32_t s, uint64_t sh,
+                                              uint64_t *lde, uint64_t *lv, uint64_t *dg, uint64_t *cp, void *ctx) {
+        return gl_commit_from_coeffs_h(hs, c, p, l, r, h, s, sh, lde, lv, dg, cp, ctx);
     }
     DeviceBuffer d_polys_, d_lde_;
 };

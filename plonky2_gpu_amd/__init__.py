@@ -1,4 +1,4 @@
-"""plonky2_gpu_amd — MI355X-native prover hot path for plonky2 (NTT/LDE, Poseidon Merkle caps,
+"""plonky2_gpu_amd — MI355X-native prover hot path for plonky2 (NTT/LDE, Poseidon and Keccak Merkle caps,
 PolynomialBatch commit) behind the reference's extern "C" boundary.
 
 The product is the HIP library `libplonky2_hip.so` (C ABI: include/plonky2_hip.h). This package is
@@ -8,7 +8,7 @@ the thin host-side mirror of the reference's operator interface for this path
 No bulk field arithmetic happens on the CPU (only scalar transcript glue such as powers of a
 challenge); without the HIP library it raises.
 """
-from ._lib import GL_E_INVALID, GL_E_UNSUPPORTED, Plonky2HipError, load  # noqa: F401
+from ._lib import GL_E_INVALID, GL_E_UNSUPPORTED, GL_HASHER_KECCAK25, GL_HASHER_POSEIDON, Plonky2HipError, load  # noqa: F401
 from .device import Context, DeviceBuffer, Event, PinnedArray  # noqa: F401
 from .fft import coset_fft, coset_ifft, coset_lde_bit_reversed, fft_with_options, ifft_with_options  # noqa: F401
 from .merkle_tree import MerkleTree  # noqa: F401

@@ -130,6 +130,22 @@ class Plonky2HipError(RuntimeError):
 GL_E_INVALID = -1
 GL_E_UNSUPPORTED = -2
 
+# include/plonky2_hip.h enum GlHasher: the hasher of a Merkle tree (the `_h` entry points)
+GL_HASHER_POSEIDON = 0
+GL_HASHER_KECCAK25 = 1
+HASHERS = {"poseidon": GL_HASHER_POSEIDON, "keccak": GL_HASHER_KECCAK25}
+KECCAK_HASH_BYTES = 25  # of a digest's 32-byte slot; the rest is zero
+
+
+def hasher_id(hasher):
+    """"poseidon" / "keccak" (or a GL_HASHER_* value) -> the C enum value."""
+    if isinstance(hasher, str):
+        if hasher not in HASHERS:
+            raise ValueError(f"unknown hasher {hasher!r}: one of {sorted(HASHERS)}")
+        return HASHERS[hasher]
+    return int(hasher)
+
+
 _vp, _u64, _u32, _i = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
 
 # name -> (restype, argtypes); every symbol declared in include/plonky2_hip.h
@@ -195,6 +211,12 @@ SIGNATURES = {
     "gl_commit_from_coeffs": (GlError, [_vp, _u64, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gl_debug_field_op": (GlError, [_i, _vp, _vp, _vp, _u64, _vp]),
     "gl_commit_from_values": (GlError, [_vp, _u64, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    # Keccak Merkle trees and commits: the calls above with the hasher as first argument
+    "gl_keccak_hash_no_pad_batch": (GlError, [_vp, _u32, _u64, _u64, _vp, _vp]),
+    "gl_merkle_tree_from_columns_h": (GlError, [_u32, _vp, _u32, _u64, _u64, _u32, _vp, _vp, _vp]),
+    "gl_merkle_tree_from_leaves_h": (GlError, [_u32, _vp, _u32, _u64, _u32, _vp, _vp, _vp]),
+    "gl_commit_from_coeffs_h": (GlError, [_u32, _vp, _u64, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gl_commit_from_values_h": (GlError, [_u32, _vp, _u64, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     # the reference's extern "C" surface (cuda/src/lib.rs:58-145)
     "init": (None, []),
     "ifft": (GlError, [_vp, _i, _i, _i, _vp, _vp, _vp]),

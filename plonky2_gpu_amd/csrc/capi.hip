@@ -13,6 +13,7 @@
 #include "../../include/plonky2_hip.h"
 #include "gl_field.h"
 #include "knobs.h"
+#include "keccak.h"
 #include "merkle.h"
 #include "ntt.h"
 #include "ntt_kernels.h"
@@ -611,6 +612,63 @@ GlError commit_from_coeffs_impl(const uint64_t *d_coeffs, uint64_t poly_num, uin
     return ok();
 }
 
+const char *const KECCAK_LEAF_LEN_4 = "KeccakHash<25>::hash_or_noop is undefined for leaves of 4 elements (plonk/config.rs:58-63 panics)";
+
+// what both Keccak commits refuse, before anything is launched (gl_commit_from_values_h: before d_values is transformed in place)
+const char *keccak_commit_argument_error(const uint64_t *d_coeffs, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height,
+                                         uint32_t salt_size, const uint64_t *d_lde, const uint64_t *d_digests, const uint64_t *d_cap, const void *ctx) {
+    if (!d_coeffs || !d_lde || !d_cap || !ctx) return "null pointer";
+    if (log_n > 24) return "log_n > 24 is not supported by this build";
+    if (log_n + rate_bits > 32 || cap_height > log_n + rate_bits) return "cap_height should be at most log2(leaves.len())";
+    if (cap_height < log_n + rate_bits && !d_digests) return "null pointer";
+    if (poly_num + salt_size == 0 || poly_num + salt_size > 0xFFFFFFFFull) return "bad poly_num";
+    if (poly_num + salt_size == 4) return KECCAK_LEAF_LEN_4;
+    return nullptr;
+}
+
+// gl_commit_from_coeffs with the Keccak tree (gl_commit_from_coeffs_h): the LDE of all columns on the caller's stream, then the
+// leaf-major transposition on stream2 side by side with the tree on the caller's stream. Not pipelined by column chunks like
+// the Poseidon commit above: the leaf kernel is shorter than the LDE, so hashing is not what an overlap
+// could hide, and a Keccak sponge cut between launches would have to carry 25 lanes per leaf.
+// d_leaves may overlap d_coeffs: the transposition starts after the last LDE launch, which is the last reader of d_coeffs.
+GlError commit_from_coeffs_keccak(const uint64_t *d_coeffs, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height,
+                                  uint32_t salt_size, uint64_t shift, uint64_t *d_lde, uint64_t *d_leaves, uint64_t *d_digests,
+                                  uint64_t *d_cap, Streams *s) {
+    if (const char *why = keccak_commit_argument_error(d_coeffs, poly_num, log_n, rate_bits, cap_height, salt_size, d_lde, d_digests, d_cap, s))
+        return fail(GL_E_INVALID, why);
+    const uint64_t n = 1ull << log_n, n_ext = n << rate_bits;
+    const uint32_t leaf_len = (uint32_t)(poly_num + salt_size);
+    const NttTables *tb;
+    CosetLease ct;
+    HIP_TRY(get_tables(s, &tb));
+    HIP_TRY(get_coset_tables(log_n, rate_bits, shift, s->stream, &ct));
+    if (salt_size) {  // see commit_from_coeffs_impl
+        const uint64_t words = (uint64_t)salt_size * n_ext, blocks = (words + 255) / 256;
+        hipLaunchKernelGGL(canon_in_place_kernel, dim3((unsigned)std::min<uint64_t>(blocks, 8192)), dim3(256), 0, s->stream,
+                           d_lde + poly_num * n_ext, words);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(coset_lde_batch(*tb, *ct, d_coeffs, d_lde, poly_num, n, n_ext, s->stream));
+    bool on_stream2 = false;
+    auto rest = [&]() -> GlError {
+        hipEvent_t ev_lde = nullptr, ev_tr = nullptr;
+        if (d_leaves) {
+            HIP_TRY(get_events(s, &ev_lde, &ev_tr));
+            HIP_TRY(hipEventRecord(ev_lde, s->stream));
+            HIP_TRY(hipStreamWaitEvent(s->stream2, ev_lde, 0));
+            on_stream2 = true;
+            HIP_TRY(transpose_to_leaf_major(d_lde, d_leaves, leaf_len, n_ext, n_ext, s->stream2));
+            HIP_TRY(hipEventRecord(ev_tr, s->stream2));
+        }
+        HIP_TRY(keccak_merkle_tree(d_lde, 1, n_ext, leaf_len, n_ext, cap_height, d_digests, d_cap, s->stream));
+        if (d_leaves) HIP_TRY(hipStreamWaitEvent(s->stream, ev_tr, 0));  // the caller's stream continues after the tree and the leaves
+        return ok();
+    };
+    GlError r = rest();
+    if (r.code != 0 && on_stream2) (void)hipStreamSynchronize(s->stream2);  // a failing call leaves nothing running behind the caller's back
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1187,6 +1245,69 @@ GlError gl_commit_from_values(uint64_t *d_values, uint64_t poly_num, uint32_t lo
     if (e.code) return e;
     return gl_commit_from_coeffs(d_values, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves,
                                  d_digests, d_cap, ctx);
+}
+
+GlError gl_keccak_hash_no_pad_batch(const uint64_t *d_inputs, uint32_t len, uint64_t stride, uint64_t count, uint64_t *d_out, void *ctx) {
+    DeviceCall device_call(ctx);
+    if (!ctx || !d_out || (!d_inputs && len)) return fail(GL_E_INVALID, "null pointer");
+    if (count > 1 && stride < len) return fail(GL_E_INVALID, "stride smaller than len: the inputs would overlap");
+    if ((uintptr_t)d_out & 15) return fail(GL_E_INVALID, "d_out must be 16-byte aligned");
+    if (count > (1ull << 40)) return fail(GL_E_INVALID, "count too large");
+    HIP_TRY(keccak_hash_no_pad_batch(d_inputs, len, stride, count, d_out, S(ctx)->stream));
+    return ok();
+}
+
+GlError gl_merkle_tree_from_columns_h(uint32_t hasher, const uint64_t *d_cols, uint32_t leaf_len, uint64_t n_leaves, uint64_t col_stride,
+                                      uint32_t cap_height, uint64_t *d_digests, uint64_t *d_cap, void *ctx) {
+    if (hasher == GL_HASHER_POSEIDON) return gl_merkle_tree_from_columns(d_cols, leaf_len, n_leaves, col_stride, cap_height, d_digests, d_cap, ctx);
+    if (hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
+    DeviceCall device_call(ctx);
+    if (!ctx || (!d_cols && leaf_len) || !d_cap) return fail(GL_E_INVALID, "null pointer");
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return fail(GL_E_INVALID, "n_leaves must be a power of two");
+    if (cap_height > 63 || (1ull << cap_height) > n_leaves) return fail(GL_E_INVALID, "cap_height should be at most log2(leaves.len())");
+    if ((1ull << cap_height) < n_leaves && !d_digests) return fail(GL_E_INVALID, "null pointer");
+    if (leaf_len > 1 && col_stride < n_leaves) return fail(GL_E_INVALID, "col_stride smaller than n_leaves: the columns would overlap");
+    if (leaf_len == 4) return fail(GL_E_INVALID, KECCAK_LEAF_LEN_4);
+    HIP_TRY(keccak_merkle_tree(d_cols, 1, col_stride, leaf_len, n_leaves, cap_height, d_digests, d_cap, S(ctx)->stream));
+    return ok();
+}
+
+GlError gl_merkle_tree_from_leaves_h(uint32_t hasher, const uint64_t *d_rows, uint32_t leaf_len, uint64_t n_leaves, uint32_t cap_height,
+                                     uint64_t *d_digests, uint64_t *d_cap, void *ctx) {
+    if (hasher == GL_HASHER_POSEIDON) return gl_merkle_tree_from_leaves(d_rows, leaf_len, n_leaves, cap_height, d_digests, d_cap, ctx);
+    if (hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
+    DeviceCall device_call(ctx);
+    if (!ctx || (!d_rows && leaf_len) || !d_cap) return fail(GL_E_INVALID, "null pointer");
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return fail(GL_E_INVALID, "n_leaves must be a power of two");
+    if (cap_height > 63 || (1ull << cap_height) > n_leaves) return fail(GL_E_INVALID, "cap_height should be at most log2(leaves.len())");
+    if ((1ull << cap_height) < n_leaves && !d_digests) return fail(GL_E_INVALID, "null pointer");
+    if (leaf_len == 4) return fail(GL_E_INVALID, KECCAK_LEAF_LEN_4);
+    HIP_TRY(keccak_merkle_tree(d_rows, leaf_len, 1, leaf_len, n_leaves, cap_height, d_digests, d_cap, S(ctx)->stream));
+    return ok();
+}
+
+GlError gl_commit_from_coeffs_h(uint32_t hasher, const uint64_t *d_coeffs, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
+                                uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde, uint64_t *d_leaves,
+                                uint64_t *d_digests, uint64_t *d_cap, void *ctx) {
+    if (hasher == GL_HASHER_POSEIDON)
+        return gl_commit_from_coeffs(d_coeffs, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves, d_digests, d_cap, ctx);
+    if (hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
+    DeviceCall device_call(ctx);
+    return commit_from_coeffs_keccak(d_coeffs, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves, d_digests, d_cap, S(ctx));
+}
+
+GlError gl_commit_from_values_h(uint32_t hasher, uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
+                                uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde, uint64_t *d_leaves,
+                                uint64_t *d_digests, uint64_t *d_cap, void *ctx) {
+    if (hasher == GL_HASHER_POSEIDON)
+        return gl_commit_from_values(d_values, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves, d_digests, d_cap, ctx);
+    if (hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
+    DeviceCall device_call(ctx);
+    if (const char *why = keccak_commit_argument_error(d_values, poly_num, log_n, rate_bits, cap_height, salt_size, d_lde, d_digests, d_cap, ctx))
+        return fail(GL_E_INVALID, why);
+    GlError e = gl_ntt_batch(d_values, poly_num, log_n, 1ull << log_n, 1, 0, ctx);
+    if (e.code) return e;
+    return gl_commit_from_coeffs_h(hasher, d_values, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves, d_digests, d_cap, ctx);
 }
 
 GlError gl_debug_copy(void *d_dst, const void *d_src, uint64_t bytes, void *ctx) {

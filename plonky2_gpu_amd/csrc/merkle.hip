@@ -18,6 +18,7 @@
 // fully coalesced without materialising the leaf-major matrix first.
 #include "merkle.h"
 #include "knobs.h"
+#include "merkle_layout.h"  // digest_slot: the digest indices, shared with keccak.hip
 
 #include <mutex>
 
@@ -52,12 +53,6 @@ __device__ __forceinline__ void store_row_block(uint64_t *dst, const uint64_t (&
         for (int q = 0; q < 3; q++) reinterpret_cast<u64x2 *>(dst + 1)[q] = u64x2{s[2 * q + 1], s[2 * q + 2]};
         dst[7] = s[7];
     }
-}
-
-// hash index (in units of 4 u64) of node `idx` of layer L inside a cap subtree
-__device__ __forceinline__ uint64_t digest_slot(uint64_t idx, uint32_t L) {
-    uint64_t q = idx >> 1, parity = idx & 1;
-    return 2 * ((q << (L + 1)) + (1ull << L) - 1) + parity;
 }
 
 // H::hash_or_noop on every row of a column-major matrix (plonky2/src/plonk/config.rs:56-67,

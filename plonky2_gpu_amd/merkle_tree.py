@@ -12,10 +12,12 @@ def _log2_strict(n):
 
 
 class MerkleTree:
-    """MerkleTree<F, PoseidonHash> (merkle_tree.rs:41-70): `digests` in the reference layout,
-    `cap` = 2^cap_height subtree roots. Leaves stay in HBM."""
+    """MerkleTree<F, PoseidonHash> or MerkleTree<F, KeccakHash<25>> (merkle_tree.rs:41-70): `digests` in the reference
+    layout, `cap` = 2^cap_height subtree roots. Leaves stay in HBM. Either hasher's digest is a slot of 4 u64 (`digests`, `cap`,
+    `prove`, `open_batch` return slots); a Keccak hash is the first 25 bytes of its slot: digest_bytes() / cap_bytes()."""
 
-    def __init__(self, ctx, n_leaves, leaf_len, cap_height, digests_buf, cap_buf, leaves_buf=None, cols_buf=None, col_stride=None):
+    def __init__(self, ctx, n_leaves, leaf_len, cap_height, digests_buf, cap_buf, leaves_buf=None, cols_buf=None, col_stride=None,
+                 hasher="poseidon"):
         self.ctx = ctx
         self.n_leaves = n_leaves
         self.leaf_len = leaf_len
@@ -25,12 +27,15 @@ class MerkleTree:
         self.d_leaves = leaves_buf  # leaf-major [n_leaves][leaf_len] or None
         self.d_cols = cols_buf  # column-major [leaf_len][col_stride] (the LDE the tree was built from) or None
         self.col_stride = col_stride
+        self.hasher = hasher
         self._digests = None
         self._cap = None
 
     @classmethod
-    def new(cls, ctx, leaves, cap_height):
-        """MerkleTree::new(leaves, cap_height) (merkle_tree.rs:283-319); leaves [n_leaves, leaf_len]."""
+    def new(cls, ctx, leaves, cap_height, hasher="poseidon"):
+        """MerkleTree::new(leaves, cap_height) (merkle_tree.rs:283-319); leaves [n_leaves, leaf_len].
+        hasher: "poseidon" (PoseidonGoldilocksConfig) or "keccak" (KeccakGoldilocksConfig)."""
+        hid = _lib.hasher_id(hasher)
         lv = np.ascontiguousarray(leaves, dtype=np.uint64)
         n, ll = lv.shape
         if cap_height > _log2_strict(n):
@@ -39,8 +44,11 @@ class MerkleTree:
         d_leaves = DeviceBuffer.from_host(ctx, lv)
         d_dig = DeviceBuffer(ctx, 4 * 2 * (n - (1 << cap_height)))
         d_cap = DeviceBuffer(ctx, 4 << cap_height)
-        _lib.call("gl_merkle_tree_from_leaves", d_leaves.ptr, ll, n, cap_height, d_dig.ptr, d_cap.ptr, ctx.ptr)
-        return cls(ctx, n, ll, cap_height, d_dig, d_cap, d_leaves)
+        if hid == _lib.GL_HASHER_POSEIDON:
+            _lib.call("gl_merkle_tree_from_leaves", d_leaves.ptr, ll, n, cap_height, d_dig.ptr, d_cap.ptr, ctx.ptr)
+        else:
+            _lib.call("gl_merkle_tree_from_leaves_h", hid, d_leaves.ptr, ll, n, cap_height, d_dig.ptr, d_cap.ptr, ctx.ptr)
+        return cls(ctx, n, ll, cap_height, d_dig, d_cap, d_leaves, hasher=hasher)
 
     @property
     def digests(self):
@@ -53,6 +61,23 @@ class MerkleTree:
         if self._cap is None:
             self._cap = self.d_cap.download(0, 4 << self.cap_height).reshape(-1, 4)
         return self._cap
+
+    @staticmethod
+    def _hash_bytes(slots):
+        b = np.ascontiguousarray(slots, dtype=np.uint64).astype("<u8").view(np.uint8).reshape(-1, 32)
+        return b[:, : _lib.KECCAK_HASH_BYTES].copy()
+
+    def digest_bytes(self):
+        """the digests of a Keccak tree as the reference holds them: uint8 [2 (n_leaves - 2^cap_height), 25] (BytesHash<25>)"""
+        if _lib.hasher_id(self.hasher) != _lib.GL_HASHER_KECCAK25:
+            raise ValueError("digest_bytes() is the view of a Keccak tree; a Poseidon digest is four field elements")
+        return self._hash_bytes(self.digests)
+
+    def cap_bytes(self):
+        """the cap of a Keccak tree: uint8 [2^cap_height, 25]"""
+        if _lib.hasher_id(self.hasher) != _lib.GL_HASHER_KECCAK25:
+            raise ValueError("cap_bytes() is the view of a Keccak tree; a Poseidon digest is four field elements")
+        return self._hash_bytes(self.cap)
 
     def get(self, i):
         """MerkleTree::get (merkle_tree.rs:385-391): leaf i, fetched from HBM."""

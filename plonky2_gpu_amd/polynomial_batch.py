@@ -10,7 +10,8 @@ SALT_SIZE = 4
 
 
 class PolynomialBatch:
-    """A batch of polynomials committed with a Poseidon Merkle cap; everything stays in HBM:
+    """A batch of polynomials committed with a Merkle cap (hasher="poseidon", or "keccak" for KeccakGoldilocksConfig: only the
+    tree differs, coefficients and LDE are the same); everything stays in HBM:
     `d_polynomials` (coefficients, [P][n]), `d_lde` (column-major bit-reversed LDE,
     [P+salt][n_ext]) and `merkle_tree` (digests, cap, optional leaf-major leaves)."""
 
@@ -26,8 +27,9 @@ class PolynomialBatch:
 
     # -- constructors -----------------------------------------------------------------------
     @classmethod
-    def _commit(cls, ctx, d_poly, from_values, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major):
+    def _commit(cls, ctx, d_poly, from_values, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major, hasher="poseidon"):
         n = 1 << log_n
+        hid = _lib.hasher_id(hasher)
         n_ext = n << rate_bits
         salt_size = SALT_SIZE if blinding else 0
         if cap_height > log_n + rate_bits:
@@ -44,17 +46,18 @@ class PolynomialBatch:
         d_leaves = DeviceBuffer(ctx, cols * n_ext) if leaf_major else None
         d_dig = DeviceBuffer(ctx, 4 * 2 * (n_ext - (1 << cap_height)))
         d_cap = DeviceBuffer(ctx, 4 << cap_height)
+        name = "gl_commit_from_values" if from_values else "gl_commit_from_coeffs"
         _lib.call(
-            "gl_commit_from_values" if from_values else "gl_commit_from_coeffs",
+            *((name,) if hid == _lib.GL_HASHER_POSEIDON else (name + "_h", hid)),
             d_poly.ptr, n_polys, log_n, rate_bits, cap_height, salt_size, COSET_SHIFT,
             d_lde.ptr, d_leaves.ptr if d_leaves else None, d_dig.ptr, d_cap.ptr, ctx.ptr,
         )
-        tree = MerkleTree(ctx, n_ext, cols, cap_height, d_dig, d_cap, d_leaves, d_lde, n_ext)
+        tree = MerkleTree(ctx, n_ext, cols, cap_height, d_dig, d_cap, d_leaves, d_lde, n_ext, hasher=hasher)
         return cls(ctx, d_poly, d_lde, tree, n_polys, log_n, rate_bits, blinding)
 
     @classmethod
     def from_values(cls, ctx, values, rate_bits, blinding, cap_height, timing=None, fft_root_table=None, salt=None,
-                    leaf_major=True):
+                    leaf_major=True, hasher="poseidon"):
         """PolynomialBatch::from_values (oracle.rs:709-731). values: [n_polys, n] evaluations on H
         (host array, uploaded) or a DeviceBuffer plus shape via from_values_device."""
         v = np.ascontiguousarray(values, dtype=np.uint64)
@@ -62,28 +65,28 @@ class PolynomialBatch:
         if n & (n - 1):
             raise ValueError("degree must be a power of two")
         d_poly = DeviceBuffer.from_host(ctx, v)
-        return cls._commit(ctx, d_poly, True, n_polys, n.bit_length() - 1, rate_bits, blinding, cap_height, salt, leaf_major)
+        return cls._commit(ctx, d_poly, True, n_polys, n.bit_length() - 1, rate_bits, blinding, cap_height, salt, leaf_major, hasher)
 
     @classmethod
     def from_coeffs(cls, ctx, polynomials, rate_bits, blinding, cap_height, timing=None, fft_root_table=None, salt=None,
-                    leaf_major=True):
+                    leaf_major=True, hasher="poseidon"):
         """PolynomialBatch::from_coeffs (oracle.rs:911-977)."""
         c = np.ascontiguousarray(polynomials, dtype=np.uint64)
         n_polys, n = c.shape
         if n & (n - 1):
             raise ValueError("degree must be a power of two")
         d_poly = DeviceBuffer.from_host(ctx, c)
-        return cls._commit(ctx, d_poly, False, n_polys, n.bit_length() - 1, rate_bits, blinding, cap_height, salt, leaf_major)
+        return cls._commit(ctx, d_poly, False, n_polys, n.bit_length() - 1, rate_bits, blinding, cap_height, salt, leaf_major, hasher)
 
     @classmethod
-    def from_values_device(cls, ctx, d_values, n_polys, log_n, rate_bits, blinding, cap_height, salt=None, leaf_major=True):
+    def from_values_device(cls, ctx, d_values, n_polys, log_n, rate_bits, blinding, cap_height, salt=None, leaf_major=True, hasher="poseidon"):
         """Same as from_values for a trace already resident in HBM (transformed in place)."""
-        return cls._commit(ctx, d_values, True, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major)
+        return cls._commit(ctx, d_values, True, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major, hasher)
 
     @classmethod
-    def from_coeffs_device(cls, ctx, d_coeffs, n_polys, log_n, rate_bits, blinding, cap_height, salt=None, leaf_major=True):
+    def from_coeffs_device(cls, ctx, d_coeffs, n_polys, log_n, rate_bits, blinding, cap_height, salt=None, leaf_major=True, hasher="poseidon"):
         """Same as from_coeffs for coefficients already resident in HBM (kept as `d_polynomials`)."""
-        return cls._commit(ctx, d_coeffs, False, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major)
+        return cls._commit(ctx, d_coeffs, False, n_polys, log_n, rate_bits, blinding, cap_height, salt, leaf_major, hasher)
 
     # -- accessors --------------------------------------------------------------------------
     @property
