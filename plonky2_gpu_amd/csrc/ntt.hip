@@ -813,6 +813,14 @@ static void base_params(PassParams &p, const NttTables &tb) {
     p.chain_scale = 1;
 }
 
+// Sweep direction of a plan's passes (PassParams::sweep_down): up, down, up. A pass then starts on the polynomials the pass before it
+// wrote last instead of on the ones written longest ago, and a caller's next transform of the same buffer starts where this one's last
+// pass ended. 64 x 2^20 natural order is 3-4 % faster for it (profiles/ntt_infinity_cache.jsonl); that the 256 MiB Infinity Cache serves
+// those first reads is the hypothesis this was built on (LABNOTES 14 says what is measured and what is not). Only the polynomial index is mirrored,
+// and only by the direct column pass and the natural-order row pass (ntt_direct.hip): a pass of any other kernel, and the block index z
+// of the three-pass plans' middle pass, walk upwards as before.
+static uint32_t sweep_of_pass(int pass) { return (uint32_t)(pass & 1); }
+
 // Passes whose global accesses are segments of T elements (column passes, transposed natural-order stores) use tiles of
 // 2^(LOGE+1) elements when the wave kernel can take them: T doubles, and so do the segments (64 -> 128 bytes at 2^20).
 // PLONKY2_NTT_WIDE=0 keeps the 8192-element tiles (A/B measurements).
@@ -925,6 +933,7 @@ hipError_t ntt_batch(const NttTables &tb, const uint64_t *src, uint64_t *dst, ui
             p.out_m = N1;
             p.flags = F_NATURAL | F_WIDE | F_FINAL_COL;
             p.log_n = log_n;
+            p.sweep_down = sweep_of_pass(1);
             e = nttk::launch_col_direct_final(p, dim3((unsigned)(N1 / C), (unsigned)cnt, 1), stream);
             if (e != hipSuccess) return e;
         }
@@ -1007,6 +1016,7 @@ hipError_t ntt_batch(const NttTables &tb, const uint64_t *src, uint64_t *dst, ui
             p.in_m = 1;
             p.out_sa = dst_stride;
             p.log_n = log_n;
+            p.sweep_down = sweep_of_pass(1);
             if (natural) {
                 p.out_sb = TB;
                 p.out_t = 1;
@@ -1089,6 +1099,7 @@ hipError_t ntt_batch(const NttTables &tb, const uint64_t *src, uint64_t *dst, ui
             p.flags = (natural ? F_NATURAL : 0) | F_RAW_OUT | (wide2 ? F_WIDE : 0);
             p.log_n = log_n;
             p.tw_hi = lb + lc;
+            p.sweep_down = sweep_of_pass(1);
             e = dispatch_pass<true>(lb, p, dim3((unsigned)(N3 / T2), (unsigned)cnt, (unsigned)N1), stream);
             if (e != hipSuccess) return e;
             base_params(p, tb);

@@ -46,6 +46,9 @@ namespace {
 #define DIRECT_NT_STORE_COL false
 #define DIRECT_NT_LOAD_ROW false
 #define DIRECT_NT_STORE_ROW false
+#define DIRECT_TOUCH_STATE
+#define DIRECT_TOUCH_COL(t_in_a)
+#define DIRECT_TOUCH_ROW(t_in_a)
 #endif
 
 __device__ __forceinline__ uint64_t lds_ld(const unsigned char *lds, uint32_t off) { return *reinterpret_cast<const uint64_t *>(lds + off); }
@@ -192,6 +195,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         const uint32_t pp = p0 + pi * pstep;
         if constexpr (COSET) a = pp / gz, z = pp % gz;
         else a = pp % gy, z = pp / gy;
+        if (p.sweep_down) a = gy - 1 - a;   // the planner alternates the direction of a plan's passes (ntt.hip, sweep_of_pass)
     };
 
     uint64_t A[16];   // tile in flight / first rounds
@@ -318,6 +322,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         }
     };
 
+    DIRECT_TOUCH_STATE
     // first rounds of the tile whose elements are in A: radix 16 over i, twiddle, exchange inside the wave, radix G over g,
     // twiddle, and the results into the exchange image; the sixteen tail steps of the previous tile are spread through it
     auto first_rounds = [&](auto WITH_TAIL_, uint32_t t_in_a) {
@@ -335,6 +340,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
             mul_run<0, 16>(A, [](auto I_) { return decltype(I_)::value; }, [&](auto I_) { return lds_ld(CU, cu_base + decltype(I_)::value * 8); }, [](auto) {});
         }
         radix_dif_stage<4, 0, 3>(A);
+        DIRECT_TOUCH_COL(t_in_a);
         TAIL(4, 6);
         radix_dif_stage<4, 0, 2>(A);
         TAIL(6, 8);
@@ -506,6 +512,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         const uint32_t r = id / gx;
         a = r % gy;
         z = r / gy;
+        if (p.sweep_down) a = gy - 1 - a;
     };
 
     uint64_t A[16];
@@ -548,12 +555,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         static_for<decltype(LO_)::value, decltype(HI_)::value>([&](auto J_) { tail_unit(J_); });
     };
 
-    auto first_rounds = [&](auto WITH_TAIL_) {
+    DIRECT_TOUCH_STATE
+    auto first_rounds = [&](auto WITH_TAIL_, uint32_t t_in_a) {   // t_in_a: the tile whose elements are in A, as in the column pass
         constexpr bool with_tail = decltype(WITH_TAIL_)::value;
         if constexpr (with_tail && DIRECT_DIAG_TAIL_FRONT_ON) tail_units(std::integral_constant<int, 0>{}, std::integral_constant<int, 16>{});
 #define TAIL(lo, hi) do { if constexpr (with_tail && !DIRECT_DIAG_TAIL_FRONT_ON) tail_units(std::integral_constant<int, lo>{}, std::integral_constant<int, hi>{}); } while (0)
         TAIL(0, 3);
         radix_dif_stage<4, 0, 3>(A);
+        DIRECT_TOUCH_ROW(t_in_a);
         TAIL(3, 5);
         radix_dif_stage<4, 0, 2>(A);
         TAIL(5, 6);
@@ -598,7 +607,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
     lds_barrier();  // tables
     issue_loads(0);
     const uint32_t last = n_tiles - 1;
-    first_rounds(std::false_type{});
+    first_rounds(std::false_type{}, 0);
     if (last > 0) issue_loads(1);
 #pragma unroll 1
     for (uint32_t k = 0; k <= last; k++) {
@@ -620,7 +629,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         else shift_twiddles_radix4<3>(B);
         tail_begin(k);
         if (k < last) {
-            first_rounds(std::true_type{});
+            first_rounds(std::true_type{}, k + 1);
             if (k + 1 < last) issue_loads(k + 2);
         } else {
             tail_units(std::integral_constant<int, 0>{}, std::integral_constant<int, 16>{});

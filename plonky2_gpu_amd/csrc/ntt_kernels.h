@@ -40,6 +40,9 @@ struct PassParams {
     uint32_t rate_bits;  // F_COSET: blockIdx.z = coset r, written to block bitrev(r)
     uint32_t row_shift;  // inverse natural-order row pass: rotate the row tile by one so that the
                          // flipped 64-byte output segments are aligned (t_limit is a power of two)
+    uint32_t sweep_down; // direct column pass and natural-order row pass only: walk the polynomials from the last to the first
+                         // (a -> gy - 1 - a, loads and stores alike; the block index z is not mirrored). The planner alternates it
+                         // between consecutive passes, so that a pass starts on what the pass before it wrote last (ntt.hip)
 };
 
 template <int I, int N, class F>

@@ -5,6 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" || exit 1
 V=$R/gpurun_in/ntt_variants
+# (the touch-ahead: VARIANTS="TOUCH_AHEAD=1 TOUCH_AHEAD=1+NT_TOUCH"; its results are right)
 VARIANTS="${VARIANTS:-SAME_LOADS SAME_STORES NO_BARRIER TAIL_FRONT SAME_LOADS+SAME_STORES SAME_LOADS+SAME_STORES+NO_BARRIER}"
 if [ "$1" = build ]; then
     make -C plonky2_gpu_amd/csrc > /dev/null || exit 1
