@@ -361,8 +361,15 @@ GlError gl_sponge_absorb(uint64_t *h_state, const uint64_t *h_inputs, uint32_t n
 typedef struct GlObserveSrc {
     const uint64_t *d_ptr;
     uint64_t count;      /* field elements observed from this source */
-    uint64_t planar_len; /* 0: d_ptr[i]; else the plane length of an extension vector kept as [2][planar_len] */
+    uint64_t planar_len; /* 0: d_ptr[i]; GL_OBSERVE_KECCAK_DIGESTS: see below; else the plane length of an extension vector kept
+                          * as [2][planar_len] */
 } GlObserveSrc;
+/* Reserved value of planar_len: d_ptr holds Keccak digests in their 32-byte slots (a cap or a digest of the `_h` trees) and the
+ * source is observed as Challenger::observe_hash::<KeccakHash<25>> / observe_cap do (BytesHash<25>::to_vec, hash/hash_types.rs:
+ * 179-189): element i is chunk i & 3 of slot i >> 2 — bytes 7c .. 7c+6 for c < 3, bytes 21 .. 24 for c = 3, little endian, zero
+ * extended. `count` stays "field elements observed", four per digest: one that is no multiple of 4 is GL_E_INVALID. Bytes 25..31
+ * of a slot are never read into the transcript. */
+#define GL_OBSERVE_KECCAK_DIGESTS UINT64_MAX
 #define GL_CHALLENGER_RESET 1u
 #define GL_CHALLENGER_HASH 2u
 GlError gl_challenger_step(uint64_t *d_challenger, const GlObserveSrc *h_srcs, uint32_t n_srcs, uint32_t n_challenges, uint64_t *d_out,
@@ -449,7 +456,7 @@ GlError gl_commit_from_values(uint64_t *d_values, uint64_t poly_num, uint32_t lo
  * The `_h` commits keep the whole contract of gl_commit_*: d_lde and d_leaves do not depend on the hasher, d_leaves may be NULL
  * or overlap d_coeffs, salt columns are reduced in place and hashed, the caller's stream continues only after the tree (and the
  * leaves), and a failing call leaves no work running on a stream other than the caller's own.
- * Not covered: gl_circuit_create / gl_prove and the reference's seven symbols are Poseidon-only. */
+ * A whole proof with this hasher: gl_circuit_create_h below. Not covered: the reference's seven symbols are Poseidon-only. */
 enum GlHasher { GL_HASHER_POSEIDON = 0, GL_HASHER_KECCAK25 = 1 };
 /* count inputs of len elements at d_inputs[i*stride ..), stride >= len when count > 1; d_out[count][4] in the slot layout above.
  * d_out 16-byte aligned. Always hash_no_pad, whatever len (0 included: the hash of the empty message). */
@@ -506,6 +513,25 @@ typedef struct GlCircuitDesc {
 } GlCircuitDesc;
 #define GL_PROVE_STAGES 11
 GlError gl_circuit_create(const GlCircuitDesc *desc, void **circuit, void *ctx);
+/* The circuit of a GenericConfig whose Hasher is `hasher` (enum GlHasher): GL_HASHER_POSEIDON forwards to gl_circuit_create, an
+ * unknown value is GL_E_INVALID and *circuit is not written. The handle carries its hasher: gl_prove, gl_prove_zk, gl_prove_many,
+ * gl_circuit_trim and gl_circuit_info take it as they take a Poseidon one. With GL_HASHER_KECCAK25 (KeccakGoldilocksConfig,
+ * plonk/config.rs:120-128: Hasher = KeccakHash<25>, InnerHasher = PoseidonHash) prove() differs from the Poseidon one in this:
+ *   - every Merkle tree — constants / sigmas, wires, Zs / partial products, quotient chunks, the FRI commit phase — is a Keccak
+ *     tree (the `_h` calls above); Merkle openings are the same, one 32-byte slot per sibling;
+ *   - the Challenger, the public-inputs hash, the proof of work and the query indices stay Poseidon (prover.rs:96, fri/prover.rs:
+ *     122-171), but observe_hash / observe_cap observe BytesHash<25>::to_vec(): four elements per hash, its bytes in chunks of
+ *     7, 7, 7 and 4 (GL_OBSERVE_KECCAK_DIGESTS) — the circuit digest, the three caps and every FRI cap;
+ *   - the circuit digest (circuit_builder.rs:915-927) is Keccak hash_no_pad(cap.flatten() || hash_pad([]).to_vec() || degree_bits);
+ *     h_circuit_digest, if given, is one 32-byte slot, and gl_circuit_info returns slots (digest: 4 u64, cap: 4 << cap_height u64;
+ *     VerifierOnlyCircuitData's hashes are the first 25 bytes of each);
+ *   - write_hash writes 25 bytes (util/serialization.rs:537-543): a cap is 2^cap_height x 25 bytes, a Merkle proof its length byte
+ *     and 25 bytes per sibling.
+ * KeccakHash<25>::hash_or_noop panics on a leaf of exactly 4 elements (plonk/config.rs:56-63), so a circuit that would build one
+ * is refused HERE with GL_E_INVALID, the message naming the cause, before anything is allocated: a commitment whose leaves have 4
+ * elements, salt included (e.g. num_challenges * quotient_degree_factor = 4 without hiding), or a FRI reduction with arity_bits = 1
+ * (leaves of 2 extension elements). */
+GlError gl_circuit_create_h(uint32_t hasher, const GlCircuitDesc *desc, void **circuit, void *ctx);
 void gl_circuit_destroy(void *circuit);
 /* gl_prove recycles its working buffers from proof to proof of the same circuit (one proof's worth of
  * HBM stays attached to the circuit PER CONTEXT that proves with it: ~10 GB at n = 2^18 with 234 wires, plus a
@@ -515,7 +541,7 @@ void gl_circuit_destroy(void *circuit);
  * device where the HOST computes with a challenge (betas / gammas, alphas, zeta, the FRI alpha), for the
  * proof-of-work witness, and once for everything that goes into the proof bytes. */
 GlError gl_circuit_trim(void *circuit);
-/* circuit digest (4) and constants_sigmas cap (4 << cap_height): what VerifierOnlyCircuitData holds */
+/* circuit digest (4) and constants_sigmas cap (4 << cap_height): what VerifierOnlyCircuitData holds (a Keccak circuit: digest slots) */
 GlError gl_circuit_info(const void *circuit, uint64_t *h_digest, uint64_t *h_constants_sigmas_cap);
 GlError gl_prove(const void *circuit, const uint64_t *d_wires, const uint64_t *h_public_inputs, uint32_t num_public_inputs,
                  uint8_t **proof, uint64_t *proof_len, double *h_stage_ms, void *ctx);

@@ -3,6 +3,7 @@
 //   PolynomialBatch::from_values / from_coeffs / get_lde_values   (plonky2/src/fri/oracle.rs:709-731, 911-1018)
 //   MerkleTree::new_ / prove, MerkleCap                            (plonky2/src/hash/merkle_tree.rs:283-319, 392-440)
 //   fft_with_options / ifft_with_options                           (field/src/fft.rs:58-103)
+//   Circuit (gl_circuit_create_h) / Circuit::prove                 (plonk/circuit_builder.rs:849-960, plonk/prover.rs:40-233)
 // Host containers are std::vector<uint64_t>; everything else stays in HBM. Errors (the reference
 // panics or drops them) become plonky2_hip::Error exceptions. No CPU fallback exists.
 #pragma once
@@ -264,6 +265,53 @@ class PolynomialBatch {
         return gl_commit_from_coeffs_h(hs, c, p, l, r, h, s, sh, lde, lv, dg, cp, ctx);
     }
     DeviceBuffer d_polys_, d_lde_;
+};
+
+// The circuit handle of the native prover (plonky2_hip.h "the whole prover in two calls"): gl_circuit_create_h on construction —
+// `hasher` is the GenericConfig's Hasher, which builds every Merkle tree of the circuit and its proofs — gl_circuit_destroy on
+// destruction. prove() = gl_prove: the proof in the reference's wire format (write_proof_with_public_inputs) for that config.
+class Circuit {
+  public:
+    Circuit(const Context &ctx, const GlCircuitDesc &desc, Hasher hasher = Hasher::Poseidon) : hasher_(hasher), cap_height_(desc.fri.cap_height) {
+        check(gl_circuit_create_h((uint32_t)hasher, &desc, &ptr_, ctx.get()));
+    }
+    ~Circuit() {
+        if (ptr_) gl_circuit_destroy(ptr_);
+    }
+    Circuit(const Circuit &) = delete;
+    Circuit &operator=(const Circuit &) = delete;
+    void *get() const { return ptr_; }
+    Hasher hasher() const { return hasher_; }
+    // VerifierOnlyCircuitData: one 4-word slot per hash (Keccak: keccak_hash_bytes(slot))
+    HashOut circuit_digest() const {
+        HashOut d(4);
+        check(gl_circuit_info(ptr_, d.data(), nullptr));
+        return d;
+    }
+    std::vector<uint64_t> constants_sigmas_cap() const {
+        std::vector<uint64_t> cap(4ull << cap_height_);
+        check(gl_circuit_info(ptr_, nullptr, cap.data()));
+        return cap;
+    }
+    // d_wires: [num_wires][2^degree_bits] in HBM; d_salts: the blinding of a hiding circuit (gl_prove_zk), else null
+    std::vector<uint8_t> prove(const Context &ctx, const uint64_t *d_wires, const std::vector<uint64_t> &public_inputs,
+                               const uint64_t *d_salts = nullptr) const {
+        uint8_t *bytes = nullptr;
+        uint64_t len = 0;
+        const uint64_t *pis = public_inputs.empty() ? nullptr : public_inputs.data();
+        if (d_salts)
+            check(gl_prove_zk(ptr_, d_wires, pis, (uint32_t)public_inputs.size(), d_salts, &bytes, &len, nullptr, ctx.get()));
+        else
+            check(gl_prove(ptr_, d_wires, pis, (uint32_t)public_inputs.size(), &bytes, &len, nullptr, ctx.get()));
+        std::vector<uint8_t> out(bytes, bytes + len);
+        gl_bytes_free(bytes);
+        return out;
+    }
+
+  private:
+    void *ptr_ = nullptr;
+    Hasher hasher_;
+    uint32_t cap_height_;
 };
 
 }  // namespace plonky2_hip

@@ -127,6 +127,7 @@ class Plonky2HipError(RuntimeError):
         self.code = code
 
 
+GL_OBSERVE_KECCAK_DIGESTS = (1 << 64) - 1  # GlObserveSrc.planar_len: the source holds Keccak digest slots, observed as to_vec()
 GL_E_INVALID = -1
 GL_E_UNSUPPORTED = -2
 
@@ -184,6 +185,7 @@ SIGNATURES = {
     "gl_gate_kernel_destroy": (None, [_vp]),
     "gl_gate_kernel_source": (ctypes.c_char_p, [_vp]),
     "gl_circuit_create": (GlError, [ctypes.POINTER(GlCircuitDesc), ctypes.POINTER(_vp), _vp]),
+    "gl_circuit_create_h": (GlError, [_u32, ctypes.POINTER(GlCircuitDesc), ctypes.POINTER(_vp), _vp]),
     "gl_circuit_destroy": (None, [_vp]),
     "gl_circuit_trim": (GlError, [_vp]),
     "gl_circuit_info": (GlError, [_vp, _vp, _vp]),

@@ -74,6 +74,50 @@ class Challenger:
         self.output_buffer = list(self.sponge_state[:SPONGE_RATE])
 
 
+class DeviceChallenger:
+    """The transcript in device memory (gl_challenger_step): 32 words the object owns; one `step` = one launch that observes up to
+    eight device sources in order and then draws challenges. A source is (DeviceBuffer or address, count) for plain field
+    elements, (.., count, planar_len) for an extension vector kept as two planes, or `keccak_digests(buf, n)` for n Keccak digest
+    slots, observed as Challenger::observe_hash::<KeccakHash<25>> / observe_cap do: four elements per digest, its 25 bytes in
+    chunks of 7, 7, 7 and 4 (hash/hash_types.rs:179-189)."""
+
+    RESET, HASH = 1, 2
+
+    def __init__(self, ctx):
+        from .device import DeviceBuffer
+
+        self.ctx = ctx
+        # all 32 words defined from the start: the kernel writes the sponge state, the input buffer and the two lengths (words 0..19,
+        # 28, 29) and never touches the rest, which would otherwise be whatever the allocation held
+        self.state = DeviceBuffer.from_host(ctx, np.zeros(32, dtype=np.uint64))
+        self._out = DeviceBuffer(ctx, 64)
+        self._fresh = True
+
+    @staticmethod
+    def keccak_digests(buf, n_digests, first=0):
+        """the source of `n_digests` digest slots starting at slot `first` of `buf`"""
+        ptr = buf if isinstance(buf, int) else buf.ptr
+        return (ptr + 32 * first, 4 * n_digests, _lib.GL_OBSERVE_KECCAK_DIGESTS)
+
+    def step(self, srcs=(), n_challenges=0, hash_out=False, reset=False):
+        """observe `srcs`, then get_n_challenges(n_challenges) -> list of ints; hash_out: the 4 words of hash_n_to_hash_no_pad of
+        everything observed since the reset instead (use with reset=True)"""
+        import ctypes
+
+        if n_challenges > 64:
+            raise ValueError("at most 64 challenges per step")
+        arr = (_lib.GlObserveSrc * max(1, len(srcs)))()
+        for i, s in enumerate(srcs):
+            p, count, planar = (tuple(s) + (0,))[:3]
+            arr[i] = _lib.GlObserveSrc(p if isinstance(p, int) else p.ptr, count, planar)
+        flags = (self.RESET if reset or self._fresh else 0) | (self.HASH if hash_out else 0)
+        words = 4 if hash_out else n_challenges
+        _lib.call("gl_challenger_step", self.state.ptr, ctypes.addressof(arr), len(srcs), n_challenges, self._out.ptr if words else None,
+                  flags, self.ctx.ptr)
+        self._fresh = False
+        return [int(v) for v in self._out.download(0, words)] if words else []
+
+
 def hash_no_pad(ctx, inputs):
     """hash_n_to_hash_no_pad (plonky2/src/hash/hashing.rs:81-108) of a short host vector (public
     inputs, circuit digest parts); the permutation runs on the device."""

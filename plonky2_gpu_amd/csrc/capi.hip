@@ -1110,7 +1110,10 @@ GlError gl_challenger_step(uint64_t *d_challenger, const GlObserveSrc *h_srcs, u
     uint64_t counts[8], planar[8];
     for (uint32_t i = 0; i < n_srcs; i++) {
         if (h_srcs[i].count && !h_srcs[i].d_ptr) return fail(GL_E_INVALID, "null source");
-        if (h_srcs[i].planar_len && h_srcs[i].count > 2 * h_srcs[i].planar_len) return fail(GL_E_INVALID, "a planar source holds 2 * planar_len elements");
+        if (h_srcs[i].planar_len == GL_OBSERVE_KECCAK_DIGESTS) {
+            if (h_srcs[i].count & 3) return fail(GL_E_INVALID, "a Keccak digest source is observed four elements per digest: count must be a multiple of 4");
+        } else if (h_srcs[i].planar_len && h_srcs[i].count > 2 * h_srcs[i].planar_len)
+            return fail(GL_E_INVALID, "a planar source holds 2 * planar_len elements");
         ptrs[i] = h_srcs[i].d_ptr, counts[i] = h_srcs[i].count, planar[i] = h_srcs[i].planar_len;
     }
     HIP_TRY(challenger_step(d_challenger, ptrs, counts, planar, n_srcs, n_challenges, flags, d_out, S(ctx)->stream));

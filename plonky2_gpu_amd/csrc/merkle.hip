@@ -310,8 +310,20 @@ __global__ __launch_bounds__(64) void sponge_absorb_kernel(uint64_t *state, cons
 struct ChallengerSrc {
     const uint64_t *p;
     uint64_t count;       // elements of this source
-    uint64_t planar_len;  // != 0: element i is p[(i & 1) * planar_len + (i >> 1)] (an extension vector kept as two planes)
+    uint64_t planar_len;  // != 0: element i is p[(i & 1) * planar_len + (i >> 1)] (an extension vector kept as two planes);
+                          // CH_KECCAK_DIGESTS: p holds 32-byte Keccak digest slots, element i is chunk i & 3 of slot i >> 2
 };
+constexpr uint64_t CH_KECCAK_DIGESTS = ~0ull;
+// BytesHash<25>::to_vec (hash/hash_types.rs:179-189): the 25 bytes of a hash in chunks of 7, 7, 7 and 4 bytes, each one field
+// element, little endian and zero extended (< 2^56: canonical). Chunk c starts at bit 56 c of the slot, so chunks 1..3 straddle
+// two of its words; bytes 25..31 of the slot (bits 200.. of word 3) are masked off whatever they hold.
+__device__ __forceinline__ uint64_t keccak_digest_chunk(const uint64_t *__restrict__ slots, uint64_t i) {
+    const uint64_t *w = slots + 4 * (i >> 2);
+    const uint32_t c = (uint32_t)i & 3, bit = 56 * c, k = bit >> 6, sh = bit & 63;
+    uint64_t v = w[k] >> sh;
+    if (sh) v |= w[k + 1] << (64 - sh);  // c = 3: k + 1 = 3, the slot's last word
+    return v & (c == 3 ? 0xFFFFFFFFull : 0x00FFFFFFFFFFFFFFull);
+}
 struct ChallengerArgs {
     ChallengerSrc src[8];
     uint32_t n_src, n_out, flags;
@@ -332,6 +344,7 @@ __global__ __launch_bounds__(64) void challenger_step_kernel(uint64_t *__restric
         for (uint32_t i = 0; i < a.n_src; i++) {
             if (g < a.src[i].count) {
                 const ChallengerSrc &sr = a.src[i];
+                if (sr.planar_len == CH_KECCAK_DIGESTS) return keccak_digest_chunk(sr.p, g);
                 return gl::canon(sr.planar_len ? sr.p[(g & 1) * sr.planar_len + (g >> 1)] : sr.p[g]);
             }
             g -= a.src[i].count;

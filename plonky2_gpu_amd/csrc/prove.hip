@@ -160,13 +160,39 @@ GlError hash_no_pad(const uint64_t *in, size_t n, uint64_t out[4], void *ctx) { 
     return ok();
 }
 
+// BytesHash<25>::to_vec (hash/hash_types.rs:179-189) of one digest slot: chunks of 7, 7, 7 and 4 bytes, little endian
+void keccak_to_vec(const uint64_t slot[4], uint64_t out[4]) {
+    uint8_t b[32];
+    memcpy(b, slot, 32);
+    for (int c = 0; c < 4; c++) {
+        out[c] = 0;
+        for (int i = 0; i < (c < 3 ? 7 : 4); i++) out[c] |= (uint64_t)b[7 * c + i] << (8 * i);
+    }
+}
+// KeccakHash<25>::hash_no_pad of a few host words, on the device (gl_keccak_hash_no_pad_batch); out = one digest slot
+GlError keccak_hash_no_pad(const std::vector<uint64_t> &in, uint64_t out[4], void *ctx) {
+    void *d = nullptr;
+    TRY(gl_malloc(&d, (in.size() + 4) * 8));  // the slot first: 16-byte aligned
+    uint64_t *p = static_cast<uint64_t *>(d);
+    GlError e = gl_memcpy_h2d(p + 4, in.data(), in.size() * 8, ctx);
+    if (e.code == 0) e = gl_keccak_hash_no_pad_batch(p + 4, (uint32_t)in.size(), in.size(), 1, p, ctx);
+    if (e.code == 0) e = gl_memcpy_d2h(out, p, 32, ctx);
+    (void)gl_free(d);
+    return e;
+}
+
 // ---- the circuit object ---------------------------------------------------------------------------
 struct Circuit {
     uint32_t degree_bits, num_wires, num_routed, num_constants, num_challenges, qdf, num_gate_constraints;
     uint32_t rate_bits, cap_height, pow_bits, num_queries;
     bool hiding = false;  // FriParams::hiding
+    uint32_t hasher = GL_HASHER_POSEIDON;  // GenericConfig::Hasher: builds every Merkle tree; the Challenger stays Poseidon (plonk/config.rs:110-128)
+    bool keccak() const { return hasher == GL_HASHER_KECCAK25; }
+    // how the transcript reads a hash of this circuit's trees: four field elements either way — a Poseidon HashOut as it lies, a
+    // Keccak digest slot through BytesHash<25>::to_vec (merkle.hip keccak_digest_chunk)
+    GlObserveSrc hashes(const uint64_t *d_slots, uint64_t words) const { return GlObserveSrc{d_slots, words, keccak() ? GL_OBSERVE_KECCAK_DIGESTS : 0}; }
     std::vector<uint32_t> arity_bits;
-    uint64_t digest[4];
+    uint64_t digest[4];  // HashOut, or one Keccak digest slot
     DevBuf k_is, sigmas;
     Batch cs;  // constants_sigmas_commitment
     // gates
@@ -216,11 +242,11 @@ GlError commit(Batch *b, DevBuf &&polys, bool from_values, uint32_t n_polys, con
     // (fri/oracle.rs:998-1002): a caller who fills d_salts with raw 64-bit randoms gets them reduced here, not >= p words on the wire.
     if (salt) TRY(canon_copy(b->lde.p + (uint64_t)n_polys * n_ext, d_salt, (uint64_t)salt * n_ext, ctx));
     if (from_values)
-        TRY(gl_commit_from_values(b->coeffs.p, n_polys, c.degree_bits, c.rate_bits, c.cap_height, salt, 7, b->lde.p, nullptr, b->digests.p,
-                                  b->cap_d.p, ctx));
+        TRY(gl_commit_from_values_h(c.hasher, b->coeffs.p, n_polys, c.degree_bits, c.rate_bits, c.cap_height, salt, 7, b->lde.p, nullptr, b->digests.p,
+                                    b->cap_d.p, ctx));
     else
-        TRY(gl_commit_from_coeffs(b->coeffs.p, n_polys, c.degree_bits, c.rate_bits, c.cap_height, salt, 7, b->lde.p, nullptr, b->digests.p,
-                                  b->cap_d.p, ctx));
+        TRY(gl_commit_from_coeffs_h(c.hasher, b->coeffs.p, n_polys, c.degree_bits, c.rate_bits, c.cap_height, salt, 7, b->lde.p, nullptr, b->digests.p,
+                                    b->cap_d.p, ctx));
     b->cap.resize(4ull << c.cap_height);
     if (!fetch_cap) return ok();  // gl_prove: the transcript reads the cap where it lies; the host copy is fetched with the rest of the proof
     return gl_memcpy_d2h(b->cap.data(), b->cap_d.p, b->cap.size() * 8, ctx);
@@ -237,9 +263,17 @@ struct Bytes {  // util/serialization.rs:466-560
         for (size_t i = 0; i < n; i++) field(p[i]);
     }
     void fields(const std::vector<uint64_t> &a) { fields(a.data(), a.size()); }
+    bool keccak = false;
+    // write_hash (:537-543) of `count` hashes in their 4-word slots: GenericHashOut::to_bytes — the four elements of a HashOut, or the
+    // first 25 bytes of a Keccak digest slot
+    void hashes(const uint64_t *slots, uint64_t count) {
+        if (!keccak) return fields(slots, 4 * count);
+        for (uint64_t h = 0; h < count; h++)
+            for (int i = 0; i < 25; i++) v.push_back((uint8_t)(slots[4 * h + (i >> 3)] >> (8 * (i & 7))));
+    }
     void merkle_proof(const uint64_t *sib, uint32_t layers) {  // :573-589
         u8((uint8_t)layers);
-        fields(sib, 4ull * layers);
+        hashes(sib, layers);
     }
 };
 
@@ -262,7 +296,7 @@ struct Stages {
 
 extern "C" {
 
-GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) {
+static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **circuit, void *ctx) {
     if (!d || !circuit || !ctx || !d->h_k_is || !d->h_constants || !d->h_sigmas || (d->fri.num_reductions && !d->fri.reduction_arity_bits))
         return fail("null pointer");
     if (d->struct_size != sizeof(GlCircuitDesc))
@@ -270,7 +304,28 @@ GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) {
     if (d->degree_bits > 24 || d->num_challenges == 0 || d->num_challenges > 4 || d->num_routed_wires > d->num_wires ||
         d->quotient_degree_factor < 2 || d->quotient_degree_factor >= d->num_routed_wires)
         return fail("bad circuit shape (the prover needs quotient_degree_factor < num_routed_wires, prover.rs:99-102)");
+    if (hasher == GL_HASHER_KECCAK25) {
+        // KeccakHash<25>::hash_or_noop panics on a leaf of exactly four elements (a 32-byte slice of a 25-byte vector, plonk/config.rs:
+        // 56-63): refuse such a circuit here, before anything is allocated, not in the middle of a proof
+        const uint32_t salt = d->fri.hiding ? SALT_SIZE : 0, nch = d->num_challenges, qdf = d->quotient_degree_factor;
+        const struct {
+            const char *name;
+            uint32_t leaf_len;
+        } commitments[4] = {{"constants / sigmas", d->num_constants + d->num_routed_wires},
+                            {"wires", d->num_wires + salt},
+                            {"Zs / partial products", nch * (1 + num_partial_products(d->num_routed_wires, qdf)) + salt},
+                            {"quotient", nch * qdf + salt}};
+        for (const auto &cm : commitments)
+            if (cm.leaf_len == 4)
+                return fail(std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
+                            " commitment have 4");
+        for (uint32_t li = 0; li < d->fri.num_reductions; li++)
+            if (d->fri.reduction_arity_bits[li] == 1)
+                return fail("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
+                            " has arity_bits = 1: its leaves are 2 extension elements");
+    }
     Circuit *c = new Circuit();
+    c->hasher = hasher;
     c->degree_bits = d->degree_bits, c->num_wires = d->num_wires, c->num_routed = d->num_routed_wires;
     c->num_constants = d->num_constants, c->num_challenges = d->num_challenges, c->qdf = d->quotient_degree_factor;
     c->num_gate_constraints = d->num_gate_constraints;
@@ -300,6 +355,16 @@ GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) {
     CTRY(commit(&c->cs, std::move(csv), true, c->num_constants + c->num_routed, *c, ctx));
     if (d->h_circuit_digest) {
         memcpy(c->digest, d->h_circuit_digest, 32);
+    } else if (c->keccak()) {
+        // the same with C::Hasher = KeccakHash<25>: cap.flatten() and the separator's hash enter as to_vec(), four elements per hash
+        const std::vector<uint64_t> pad = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+        uint64_t dsd[4];
+        CTRY(keccak_hash_no_pad(pad, dsd, ctx));
+        std::vector<uint64_t> parts(c->cs.cap.size() + 5);
+        for (size_t h = 0; h < c->cs.cap.size() / 4; h++) keccak_to_vec(c->cs.cap.data() + 4 * h, parts.data() + 4 * h);
+        keccak_to_vec(dsd, parts.data() + c->cs.cap.size());
+        parts.back() = c->degree_bits;
+        CTRY(keccak_hash_no_pad(parts, c->digest, ctx));
     } else {
         // circuit_builder.rs:915-927: hash_no_pad(cap || hash_pad(domain separator = []) || degree_bits)
         uint64_t pad[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, dsd[4];
@@ -342,6 +407,14 @@ GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) {
 #undef CTRY
     *circuit = c;
     return ok();
+}
+
+GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) { return circuit_create(GL_HASHER_POSEIDON, d, circuit, ctx); }
+
+GlError gl_circuit_create_h(uint32_t hasher, const GlCircuitDesc *d, void **circuit, void *ctx) {
+    if (hasher == GL_HASHER_POSEIDON) return gl_circuit_create(d, circuit, ctx);
+    if (hasher != GL_HASHER_KECCAK25) return fail("unknown hasher");
+    return circuit_create(hasher, d, circuit, ctx);
 }
 
 void gl_circuit_destroy(void *circuit) { delete static_cast<Circuit *>(circuit); }
@@ -475,7 +548,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     }
     TRY(st.mark(0));
     // challenger.observe_hash(circuit digest), observe_hash(public inputs hash), observe_cap(wires cap); betas, gammas (prover.rs:92-97)
-    TRY(step({GlObserveSrc{D + hostin.off, 4, 0}, GlObserveSrc{D + pih_s.off, 4, 0}, GlObserveSrc{wires.cap_d.p, cap_words, 0}}, 2 * nch, bg, GL_CHALLENGER_RESET));
+    TRY(step({c.hashes(D + hostin.off, 4), GlObserveSrc{D + pih_s.off, 4, 0}, c.hashes(wires.cap_d.p, cap_words)}, 2 * nch, bg, GL_CHALLENGER_RESET));
     TRY(fetch(Span{pih_s.off, bg.off + bg.words - pih_s.off}));
     TRY(stream_sync(ctx));
     uint64_t pih[4];
@@ -493,7 +566,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
         TRY(commit(&zs, std::move(z), true, nch * (1 + npp), c, ctx, d_salts ? d_salts + (uint64_t)SALT_SIZE * n_ext : nullptr, false));
     }
     TRY(st.mark(2));
-    TRY(step({GlObserveSrc{zs.cap_d.p, cap_words, 0}}, nch, alphas_s));
+    TRY(step({c.hashes(zs.cap_d.p, cap_words)}, nch, alphas_s));
     TRY(fetch(alphas_s));
     TRY(stream_sync(ctx));
     alphas.assign(H + alphas_s.off, H + alphas_s.off + nch);
@@ -549,7 +622,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
         TRY(commit(&quot, std::move(chunks), false, nch * qdf, c, ctx, d_salts ? d_salts + 2ull * SALT_SIZE * n_ext : nullptr, false));
     }
     TRY(st.mark(4));
-    TRY(step({GlObserveSrc{quot.cap_d.p, cap_words, 0}}, 2, zeta_s));
+    TRY(step({c.hashes(quot.cap_d.p, cap_words)}, 2, zeta_s));
     TRY(fetch(zeta_s));
     TRY(stream_sync(ctx));
     const E2 zeta{H[zeta_s.off], H[zeta_s.off + 1]};
@@ -625,9 +698,9 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
             TRY(gl_ext2_interleave(vals.p, lde_len, L.rows.p, ctx));
             TRY(L.digests.alloc(8 * (fs[li].n_leaves - (1ull << c.cap_height)) + 4));
             TRY(L.cap_d.alloc(cap_words));
-            TRY(gl_merkle_tree_from_leaves(L.rows.p, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, L.digests.p, L.cap_d.p, ctx));
+            TRY(gl_merkle_tree_from_leaves_h(c.hasher, L.rows.p, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, L.digests.p, L.cap_d.p, ctx));
             TRY(gl_memcpy_d2d(D + fri_caps.off + li * cap_words, L.cap_d.p, cap_words * 8, ctx));
-            TRY(step({GlObserveSrc{L.cap_d.p, cap_words, 0}}, 2, Span{fri_betas.off + 2ull * li, 2}));
+            TRY(step({c.hashes(L.cap_d.p, cap_words)}, 2, Span{fri_betas.off + 2ull * li, 2}));
             DevBuf next;
             TRY(next.alloc(2 * (len >> ab)));
             TRY(gl_fri_fold_device(coeffs.p, len, ab, D + fri_betas.off + 2ull * li, next.p, ctx));
@@ -667,7 +740,8 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     if (H[pow_w.off] != pow_witness) return fail("proof-of-work witness changed between the search and the transcript");
     // ---- write_proof_with_public_inputs (util/serialization.rs:641-689) ----
     Bytes out;
-    for (int o = 0; o < 3; o++) out.fields(H + caps[o].off, cap_words);  // wires, zs / partial products, quotient
+    out.keccak = c.keccak();
+    for (int o = 0; o < 3; o++) out.hashes(H + caps[o].off, cap_words / 4);  // wires, zs / partial products, quotient
     // write_opening_set (:557-571): constants, sigmas, wires, zs, zs_next, partial products, quotient
     const uint64_t *ev[4] = {H + opens[0].off, H + opens[1].off, H + opens[2].off, H + opens[3].off};
     out.fields(ev[0], 2ull * n_polys[0]);                                   // constants then sigmas: contiguous
@@ -676,7 +750,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     out.fields(ev[2] + 2ull * n_polys[2], 2ull * nch);                      // plonk_zs_next
     out.fields(ev[2] + 2ull * nch, 2ull * n_polys[2] - 2ull * nch);         // partial_products
     out.fields(ev[3], 2ull * n_polys[3]);                                   // quotient_polys
-    for (uint32_t li = 0; li < n_fri; li++) out.fields(H + fri_caps.off + li * cap_words, cap_words);
+    for (uint32_t li = 0; li < n_fri; li++) out.hashes(H + fri_caps.off + li * cap_words, cap_words / 4);
     for (uint32_t q = 0; q < nq; q++) {
         for (int o = 0; o < 4; o++) {
             out.fields(H + q_leaves[o].off + (uint64_t)q * leaf_len[o], leaf_len[o]);

@@ -154,7 +154,9 @@ class GateProgram:
 class CircuitData:
     """What prove() needs of CommonCircuitData + ProverOnlyCircuitData (plonk/circuit_data.rs), resident
     in HBM: the preprocessed constants_sigmas commitment, the sigma value columns, k_is and the gate
-    programs. `circuit` is the plain dict described in INTEGRATION.md section 7."""
+    programs. `circuit` is the plain dict described in INTEGRATION.md section 7.
+    Poseidon only (PoseidonGoldilocksConfig): this host-logic mirror and prove() below build Poseidon trees and observe HashOut
+    elements; a KeccakGoldilocksConfig circuit is proved by the native prover, NativeCircuit(.., hasher="keccak")."""
 
     def __init__(self, ctx, circuit, compile_gates=True):
         from . import gate_program as gp
@@ -199,7 +201,7 @@ def _pairs(a):
 def prove(ctx, cd, wires, public_inputs, timing=None):
     """prove() (plonk/prover.rs:40-233) from the full witness on: `wires` is the [num_wires][n] matrix of
     wire values (host array, or a DeviceBuffer that is left untouched). Every polynomial, LDE and tree
-    stays in HBM; the host sees caps, challenges, openings and the FRI proof."""
+    stays in HBM; the host sees caps, challenges, openings and the FRI proof. Poseidon only, see CircuitData."""
     import time
 
     from . import fri
@@ -283,10 +285,15 @@ class NativeCircuit:
     """The circuit object of the library's own prover (gl_circuit_create): same input dict as
     CircuitData, but the whole of prove() then runs inside one native call (gl_prove, csrc/prove.hip)."""
 
-    def __init__(self, ctx, circuit, compile_gates=True):
+    def __init__(self, ctx, circuit, compile_gates=True, hasher=_lib.GL_HASHER_POSEIDON):
+        """`hasher`: "poseidon" / "keccak" or a GL_HASHER_* value (gl_circuit_create_h) — the GenericConfig's Hasher, which builds
+        every Merkle tree of the circuit and its proofs. With Keccak (KeccakGoldilocksConfig) a hash is `bytes` of length 25:
+        circuit["circuit_digest"] if given, and the attributes circuit_digest and constants_sigmas_cap (a list of them)."""
         from . import gate_program as gp
 
         self.ctx = ctx
+        self.hasher = _lib.hasher_id(hasher)
+        keccak = self.hasher == _lib.GL_HASHER_KECCAK25
         self.circuit = circuit
         pool = gp.ImmediatePool()
         programs = [gp.build_gate(kind, param, pool) for kind, param in circuit["gates"]]
@@ -296,7 +303,9 @@ class NativeCircuit:
         fp = circuit["fri_params"]
         arity = np.ascontiguousarray(fp["reduction_arity_bits"], dtype=np.uint32)
         k_is, consts, sigmas = _host_u64(circuit["k_is"]), _host_u64(circuit["constants"]), _host_u64(circuit["sigmas"])
-        digest = _host_u64(circuit["circuit_digest"]) if circuit.get("circuit_digest") is not None else None
+        digest = circuit.get("circuit_digest")
+        if digest is not None:  # a Keccak digest travels in its 32-byte slot
+            digest = np.frombuffer(bytes(digest).ljust(32, b"\0"), dtype=np.uint64).copy() if keccak else _host_u64(digest)
         desc = _lib.GlCircuitDesc(
             ctypes.sizeof(_lib.GlCircuitDesc), circuit["degree_bits"], circuit["num_wires"], circuit["num_routed_wires"], circuit["num_constants"], circuit["num_challenges"],
             circuit["quotient_degree_factor"], circuit["num_gate_constraints"],
@@ -307,13 +316,17 @@ class NativeCircuit:
             imms.ctypes.data if imms is not None else None, 0 if imms is None else imms.size, len(circuit["groups"]),
             1 if compile_gates else 0, digest.ctypes.data if digest is not None else None)
         h = ctypes.c_void_p()
-        _lib.call("gl_circuit_create", ctypes.byref(desc), ctypes.byref(h), ctx.ptr)
+        _lib.call("gl_circuit_create_h", self.hasher, ctypes.byref(desc), ctypes.byref(h), ctx.ptr)
         self.ptr = h.value
         dg = np.zeros(4, dtype=np.uint64)
         cap = np.zeros(4 << fp["cap_height"], dtype=np.uint64)
         _lib.call("gl_circuit_info", self.ptr, dg, cap)
-        self.circuit_digest = [int(x) for x in dg]
-        self.constants_sigmas_cap = cap.reshape(-1, 4).tolist()
+        if keccak:
+            self.circuit_digest = dg.tobytes()[: _lib.KECCAK_HASH_BYTES]
+            self.constants_sigmas_cap = [row.tobytes()[: _lib.KECCAK_HASH_BYTES] for row in cap.reshape(-1, 4)]
+        else:
+            self.circuit_digest = [int(x) for x in dg]
+            self.constants_sigmas_cap = cap.reshape(-1, 4).tolist()
 
     def prove_bytes(self, wires, public_inputs, timing=None, salts=None, ctx=None):
         """gl_prove: the proof in the reference's wire format. `wires`: host [num_wires][n] or a DeviceBuffer.
@@ -360,7 +373,7 @@ class NativeCircuit:
     def prove(self, wires, public_inputs, timing=None, salts=None):
         from . import serialization
 
-        return serialization.proof_from_bytes(self.prove_bytes(wires, public_inputs, timing, salts), self.circuit)
+        return serialization.proof_from_bytes(self.prove_bytes(wires, public_inputs, timing, salts), self.circuit, self.hasher)
 
     def trim(self):
         """release the working buffers gl_prove keeps attached to the circuit between proofs"""

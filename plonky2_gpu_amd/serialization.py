@@ -1,16 +1,30 @@
 """Host-side mirror of the proof wire format (plonky2/src/util/serialization.rs:492-700 Write,
 :57-348 Read): little-endian canonical u64 per field element, extension elements as their two
-base coefficients, hashes as 4 elements, Merkle proofs with a one-byte length prefix. Pure byte
+base coefficients, hashes as 4 elements (PoseidonGoldilocksConfig) or as their 25 bytes (KeccakGoldilocksConfig: write_hash
+writes GenericHashOut::to_bytes, :537-543), Merkle proofs with a one-byte length prefix. Pure byte
 shuffling — no field arithmetic."""
 import struct
 
 P = 0xFFFFFFFF00000001
+POSEIDON, KECCAK = 0, 1  # include/plonky2_hip.h enum GlHasher
+KECCAK_HASH_BYTES = 25
+
+
+def _hasher_id(hasher):
+    if isinstance(hasher, str):
+        return {"poseidon": POSEIDON, "keccak": KECCAK}[hasher]
+    if int(hasher) not in (POSEIDON, KECCAK):
+        raise ValueError(f"unknown hasher {hasher!r}")
+    return int(hasher)
 
 
 class Buffer:
-    def __init__(self, data=b""):
+    """`hasher`: how a hash travels — a list of 4 field elements (Poseidon) or `bytes` of length 25 (Keccak)"""
+
+    def __init__(self, data=b"", hasher=POSEIDON):
         self.data = bytearray(data)
         self.pos = 0
+        self.keccak = _hasher_id(hasher) == KECCAK
 
     # -- Write (serialization.rs:466-700)
     def write_u8(self, x):
@@ -29,7 +43,12 @@ class Buffer:
             self.write_field(b)
 
     def write_hash(self, h):
-        self.write_field_vec(h)
+        if self.keccak:
+            if len(h) != KECCAK_HASH_BYTES:
+                raise ValueError("a Keccak hash is 25 bytes")
+            self.data += bytes(h)
+        else:
+            self.write_field_vec(h)
 
     def write_merkle_cap(self, cap):
         for h in cap:
@@ -69,7 +88,7 @@ class Buffer:
         return [(self.read_field(), self.read_field()) for _ in range(n)]
 
     def read_hash(self):
-        return self.read_field_vec(4)
+        return self._take(KECCAK_HASH_BYTES) if self.keccak else self.read_field_vec(4)
 
     def read_merkle_cap(self, cap_height):
         return [self.read_hash() for _ in range(1 << cap_height)]
@@ -82,9 +101,9 @@ def _num_partial_products(num_routed, qdf):
     return -(-num_routed // qdf) - 1
 
 
-def proof_to_bytes(proof):
-    """write_proof_with_public_inputs (serialization.rs:674-689)"""
-    b = Buffer()
+def proof_to_bytes(proof, hasher=POSEIDON):
+    """write_proof_with_public_inputs (serialization.rs:674-689); with hasher = KECCAK every hash of the dict is 25 `bytes`"""
+    b = Buffer(hasher=hasher)
     b.write_merkle_cap(proof["wires_cap"])
     b.write_merkle_cap(proof["plonk_zs_partial_products_cap"])
     b.write_merkle_cap(proof["quotient_polys_cap"])
@@ -107,15 +126,16 @@ def proof_to_bytes(proof):
     return bytes(b.data)
 
 
-def proof_from_bytes(data, common):
+def proof_from_bytes(data, common, hasher=POSEIDON):
     """read_proof_with_public_inputs (serialization.rs:306-348). `common` carries the shape fields of
     CommonCircuitData: num_constants, num_routed_wires, num_wires, num_challenges,
-    quotient_degree_factor, degree_bits, fri_params (with fri_params["hiding"]: salted leaves)."""
+    quotient_degree_factor, degree_bits, fri_params (with fri_params["hiding"]: salted leaves).
+    With hasher = KECCAK a hash comes back as `bytes` of length 25."""
     get = (lambda k: common[k]) if isinstance(common, dict) else (lambda k: getattr(common, k))
     fp = get("fri_params")
     nch, qdf = get("num_challenges"), get("quotient_degree_factor")
     npp = _num_partial_products(get("num_routed_wires"), qdf)
-    b = Buffer(data)
+    b = Buffer(data, hasher)
     h = fp["cap_height"]
     proof = dict(wires_cap=b.read_merkle_cap(h), plonk_zs_partial_products_cap=b.read_merkle_cap(h), quotient_polys_cap=b.read_merkle_cap(h))
     proof["openings"] = dict(
