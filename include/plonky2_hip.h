@@ -566,6 +566,79 @@ GlError gl_prove_zk(const void *circuit, const uint64_t *d_wires, const uint64_t
                     const uint64_t *d_salts, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms, void *ctx);
 void gl_bytes_free(uint8_t *p);
 
+/* ---- STARKs: starky's prove() in two calls --------------------------------------------------------
+ * gl_stark_create describes a STARK (starky/src/stark.rs), gl_stark_prove = prove() (starky/src/prover.rs:32-195) of one trace:
+ * trace commit, the permutation Z polynomials (permutation.rs) and their commit if the STARK has permutation pairs, the constraint
+ * quotient, its commit, the openings at zeta and g * zeta and PolynomialBatch::prove_openings over the instance of stark.rs:88-137 —
+ * the commit, tree, transcript and FRI code of gl_prove. This version of starky observes only the caps and the openings: neither a
+ * digest of the STARK nor the public inputs enter the transcript.
+ *
+ * The constraints (Stark::eval_packed_generic) are ONE register program for the whole STARK in the GlGateInstr encoding above — its
+ * 64 registers, its 4 ACC accumulators and their overflow contract — without GlGateDescs, selectors or filters. In a STARK program:
+ *   0 LOAD_WIRE dst<-local_values[a]      2 LOAD_PI dst<-public_inputs[a] (the public inputs themselves, any number of them)
+ *   3 LOAD_IMM  4 ADD  5 SUB  6 MUL  8 MULK  9 ACC  10 ACCR   as above         1 LOAD_CONST   invalid
+ *   7 EMIT            consumer.constraint(r[a])                11 LOAD_NEXT dst<-next_values[a]
+ *  12 EMIT_TRANSITION constraint(r[a] * z_last)                13 EMIT_FIRST_ROW constraint(r[a] * lagrange_first)
+ *  14 EMIT_LAST_ROW   constraint(r[a] * lagrange_last)
+ * Opcodes 11..14 exist in STARK programs only: gate programs refuse them as they refuse any unknown opcode. The consumer is starky's
+ * (constraint_consumer.rs:53-76), not plonk's reduce_with_powers: for every challenge acc <- acc * alpha + constraint in emission
+ * order. gl_stark_create validates the program once, on the host: no LOAD_CONST or unknown opcode, columns / public inputs /
+ * immediates / registers in range, every register written before it is read, the ACC contract, at least one EMIT.
+ *
+ * Permutation pairs (PermutationPair::column_pairs): pair p is the column pairs h_pair_bounds[p] .. h_pair_bounds[p + 1] of
+ * h_column_pairs, two words (lhs, rhs) each. The instances cartesian_product(pairs, 0..num_challenges) are batched by
+ * quotient_degree_factor = max(1, constraint_degree - 1) into num_z = ceil(num_pairs * num_challenges / qdf) Z polynomials.
+ *
+ * fri.hiding must be 0 (starky: fri_params(degree_bits, false)); log2_ceil(qdf) <= fri.rate_bits; num_challenges <= 4; qdf <= 16.
+ * With GL_HASHER_KECCAK25 a commitment with 4-element leaves (num_columns = 4, num_z = 4, num_challenges * qdf = 4) or a FRI
+ * reduction with arity_bits = 1 is refused here, as by gl_circuit_create_h. Every refusal is GL_E_INVALID with a message, before
+ * anything is allocated. */
+typedef struct GlStarkDesc {
+    uint32_t struct_size; /* = sizeof(GlStarkDesc) of the header the caller was compiled against, as in GlCircuitDesc */
+    uint32_t degree_bits, num_columns, num_public_inputs, constraint_degree, num_challenges;
+    GlFriParams fri;
+    const GlGateInstr *h_instrs;
+    uint32_t num_instrs;
+    const uint64_t *h_immediates;
+    uint32_t num_immediates;
+    const uint32_t *h_column_pairs; /* 2 * h_pair_bounds[num_pairs] words; NULL without pairs */
+    const uint32_t *h_pair_bounds;  /* num_pairs + 1, starting at 0, non-decreasing; NULL without pairs */
+    uint32_t num_pairs;
+} GlStarkDesc;
+/* h_stage_ms of gl_stark_prove: trace commit, permutation Zs, Z commit, quotient, quotient commit, openings, FRI combine, FRI commit
+ * phase, proof of work, query rounds, serialisation */
+#define GL_STARK_STAGES 11
+GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *desc, void **stark, void *ctx);
+void gl_stark_destroy(void *stark);
+/* releases the recycled working buffers of the handle's proofs (one pool per context, as gl_circuit_trim); only between proofs */
+GlError gl_stark_trim(void *stark);
+/* d_trace: [num_columns][2^degree_bits] value columns, left untouched; h_public_inputs: num_public_inputs words. The proof comes
+ * back in a malloc'd buffer (gl_bytes_free). WIRE FORMAT of StarkProofWithPublicInputs (the reference has no serializer for it):
+ * the fields in struct order (starky/src/proof.rs:23-35, 129-135) with the primitives of plonky2/src/util/serialization.rs —
+ *   trace_cap; permutation_zs_cap only if the STARK has pairs (no flag byte: the description decides); quotient_polys_cap —
+ *     2^cap_height hashes each (write_hash: 4 field elements, or 25 bytes with GL_HASHER_KECCAK25);
+ *   the openings, extension elements as two field elements: local_values, next_values, [permutation_zs, permutation_zs_next,]
+ *     quotient_polys;
+ *   the FRI proof exactly as write_fri_proof writes it (the bytes gl_prove emits for that part);
+ *   the public inputs.
+ * A trace that violates the constraints gives GL_E_INVALID "Quotient has failed..." where the reference's trim_to_len can fail
+ * (qdf no power of two); otherwise, as in the reference, a proof that no verifier accepts. */
+GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_t *h_public_inputs, uint8_t **proof, uint64_t *proof_len,
+                       double *h_stage_ms, void *ctx);
+/* The two kernels of gl_stark_prove alone, with host challenges. h_challenges: the qdf challenge sets in the order they are drawn
+ * (permutation.rs:153-179): (beta, gamma) of set s, challenge c at h_challenges[2 * (s * num_challenges + c)].
+ * gl_stark_permutation_zs: d_trace value columns at pitch trace_stride >= n -> d_zs [num_z][n] value columns
+ * (compute_permutation_z_polys). GL_E_INVALID for a STARK without pairs. */
+GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
+                                void *ctx);
+/* gl_stark_quotient_polys: compute_quotient_polys (prover.rs:199-319). d_trace_lde / d_zs_lde: the d_lde of gl_commit_from_values of
+ * the trace and of the Zs (NULL without pairs), column-major at pitch column_stride >= n << rate_bits, rows in bit-reversed order;
+ * h_alphas: num_challenges; h_challenges: as above (NULL without pairs); h_public_inputs: num_public_inputs.
+ * d_quotient_polys [num_challenges][n << log2_ceil(qdf)] receives the COEFFICIENTS (after the coset_ifft). */
+GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
+                                const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
+                                uint64_t *d_quotient_polys, void *ctx);
+
 /* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */

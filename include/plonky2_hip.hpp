@@ -314,4 +314,34 @@ class Circuit {
     uint32_t cap_height_;
 };
 
+// The STARK handle (plonky2_hip.h "STARKs: starky's prove() in two calls"): gl_stark_create on construction, gl_stark_destroy on
+// destruction. prove() = gl_stark_prove: StarkProofWithPublicInputs in the wire format the header defines.
+class Stark {
+  public:
+    Stark(const Context &ctx, const GlStarkDesc &desc, Hasher hasher = Hasher::Poseidon) : num_public_inputs_(desc.num_public_inputs) {
+        check(gl_stark_create((uint32_t)hasher, &desc, &ptr_, ctx.get()));
+    }
+    ~Stark() {
+        if (ptr_) gl_stark_destroy(ptr_);
+    }
+    Stark(const Stark &) = delete;
+    Stark &operator=(const Stark &) = delete;
+    void *get() const { return ptr_; }
+    // d_trace: [num_columns][2^degree_bits] value columns in HBM
+    std::vector<uint8_t> prove(const Context &ctx, const uint64_t *d_trace, const std::vector<uint64_t> &public_inputs) const {
+        if (public_inputs.size() != num_public_inputs_) throw std::invalid_argument("Stark::prove: wrong number of public inputs");
+        uint8_t *bytes = nullptr;
+        uint64_t len = 0;
+        check(gl_stark_prove(ptr_, d_trace, public_inputs.empty() ? nullptr : public_inputs.data(), &bytes, &len, nullptr, ctx.get()));
+        std::vector<uint8_t> out(bytes, bytes + len);
+        gl_bytes_free(bytes);
+        return out;
+    }
+    void trim() const { check(gl_stark_trim(ptr_)); }
+
+  private:
+    void *ptr_ = nullptr;
+    uint32_t num_public_inputs_;
+};
+
 }  // namespace plonky2_hip

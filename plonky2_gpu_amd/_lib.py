@@ -116,7 +116,29 @@ class GlCircuitDesc(ctypes.Structure):
     ]
 
 
+class GlStarkDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("degree_bits", ctypes.c_uint32),
+        ("num_columns", ctypes.c_uint32),
+        ("num_public_inputs", ctypes.c_uint32),
+        ("constraint_degree", ctypes.c_uint32),
+        ("num_challenges", ctypes.c_uint32),
+        ("fri", GlFriParams),
+        ("h_instrs", ctypes.c_void_p),
+        ("num_instrs", ctypes.c_uint32),
+        ("h_immediates", ctypes.c_void_p),
+        ("num_immediates", ctypes.c_uint32),
+        ("h_column_pairs", ctypes.c_void_p),
+        ("h_pair_bounds", ctypes.c_void_p),
+        ("num_pairs", ctypes.c_uint32),
+    ]
+
+
 GL_PROVE_STAGES = 11
+GL_STARK_STAGES = 11
+STARK_STAGE_NAMES = ["trace commitment", "permutation zs", "zs commitment", "quotient polys", "quotient commitment", "opening set",
+                     "fri: combine + divide", "fri: commit phase", "fri: proof of work", "fri: query rounds", "serialise"]
 PROVE_STAGE_NAMES = ["wires commitment", "partial products", "zs partial products commitment", "quotient polys", "quotient commitment",
                      "opening set", "fri: combine + divide", "fri: commit phase", "fri: proof of work", "fri: query rounds", "serialise"]
 
@@ -193,6 +215,12 @@ SIGNATURES = {
     "gl_prove_many": (GlError, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32]),
     "gl_prove_zk": (GlError, [_vp, _vp, _vp, _u32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
     "gl_bytes_free": (None, [_vp]),
+    "gl_stark_create": (GlError, [_u32, ctypes.POINTER(GlStarkDesc), ctypes.POINTER(_vp), _vp]),
+    "gl_stark_destroy": (None, [_vp]),
+    "gl_stark_trim": (GlError, [_vp]),
+    "gl_stark_prove": (GlError, [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
+    "gl_stark_permutation_zs": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "gl_stark_quotient_polys": (GlError, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

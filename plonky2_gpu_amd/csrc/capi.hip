@@ -18,6 +18,7 @@
 #include "ntt.h"
 #include "ntt_kernels.h"
 #include "plonk.h"
+#include "stark.h"
 #include "fri.h"
 #include "ed25519_gate_program.inc"
 
@@ -670,6 +671,14 @@ GlError commit_from_coeffs_keccak(const uint64_t *d_coeffs, uint64_t poly_num, u
 }
 
 }  // namespace
+
+// stark.h: the tables and the workspace of a context for callers outside this file (the STARK entry points of prove.hip), its device
+// made current like in every entry point here
+hipError_t plonky2_hip::ctx_tables(void *ctx, const NttTables **out) {
+    if (!ctx) return hipErrorInvalidValue;
+    DeviceCall device_call(ctx);
+    return get_tables(ctx, out);
+}
 
 extern "C" {
 

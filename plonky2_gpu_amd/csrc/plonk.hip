@@ -15,6 +15,7 @@
 #include "plonk.h"
 
 #include "gl_field.h"
+#include "plonk_device.h"
 
 namespace plonky2_hip {
 
@@ -27,27 +28,7 @@ struct Challenges {
     uint64_t beta[MAX_CHALLENGES], gamma[MAX_CHALLENGES], alpha[MAX_CHALLENGES];
 };
 
-// w_{2^log}^i through the two-level table of w_{2^24}
-__device__ __forceinline__ uint64_t root_pow(const uint64_t *twl, const uint64_t *twh, uint32_t log, uint64_t i) {
-    uint32_t e = (uint32_t)(i << (24 - log)) & 0xFFFFFFu;
-    uint64_t h = twh[e >> 12];
-    uint32_t lo = e & 4095u;
-    return lo ? gl::mul(h, twl[lo]) : h;
-}
-
-__device__ __forceinline__ uint64_t inverse(uint64_t x) { return gl::pow(x, gl::P - 2); }
-
-// x^(p-2): with e_k = x^(2^k - 1), p - 2 = (2^31 - 1) 2^33 + (2^32 - 1)
-__device__ __forceinline__ uint64_t inverse_chain(uint64_t x) {
-    auto sqn = [](uint64_t v, int k) {
-        for (int i = 0; i < k; i++) v = gl::sqr(v);
-        return v;
-    };
-    const uint64_t e2 = gl::mul(gl::sqr(x), x), e3 = gl::mul(gl::sqr(e2), x), e6 = gl::mul(sqn(e3, 3), e3), e12 = gl::mul(sqn(e6, 6), e6);
-    const uint64_t e15 = gl::mul(sqn(e12, 3), e3), e30 = gl::mul(sqn(e15, 15), e15), e31 = gl::mul(gl::sqr(e30), x), e32 = gl::mul(gl::sqr(e31), x);
-    return gl::mul(sqn(e31, 33), e32);
-}
-
+// root_pow, inverse, inverse_chain and the exclusive prefix product over rows (scan_blocks_kernel, scan_totals_kernel): plonk_device.h
 
 // One thread per (row i, challenge c): cumulative chunk quotients c_k(i) = prod_{m<=k} q_m(i) written to
 // the partial-product slots (k < num_prods) and the row total r_i to the Z slot.
@@ -114,63 +95,6 @@ __global__ __launch_bounds__(256) void perm_quotients_kernel(const uint64_t *__r
         chunk(k, num, den);
         cum = gl::mul(cum, gl::mul(num, inverse(den)));
         store(k, cum);
-    }
-}
-
-// ---- exclusive prefix product over rows (three kernels) ---------------------------------------
-constexpr int SCAN_T = 256, SCAN_E = 4, SCAN_B = SCAN_T * SCAN_E;
-
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t *lds, uint64_t *total) {
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_T; off <<= 1) {
-        uint64_t x = (t >= (uint32_t)off) ? gl::mul(lds[t - off], lds[t]) : lds[t];
-        __syncthreads();
-        lds[t] = x;
-        __syncthreads();
-    }
-    uint64_t incl = lds[t];
-    uint64_t excl = t ? lds[t - 1] : 1;
-    if (total && t == SCAN_T - 1) *total = incl;
-    __syncthreads();
-    return excl;
-}
-
-// in place: v[i] <- product of the block's earlier elements; totals[blk] <- product of the block
-__global__ __launch_bounds__(SCAN_T) void scan_blocks_kernel(uint64_t *v, uint64_t n, uint64_t col_stride, uint64_t *totals,
-                                                             uint64_t totals_stride) {
-    __shared__ uint64_t lds[SCAN_T];
-    uint64_t *col = v + (uint64_t)blockIdx.y * col_stride;
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_B + (uint64_t)threadIdx.x * SCAN_E;
-    uint64_t e[SCAN_E];
-    uint64_t p = 1;
-#pragma unroll
-    for (int k = 0; k < SCAN_E; k++) {
-        e[k] = base + k < n ? col[base + k] : 1;
-        p = gl::mul(p, e[k]);
-    }
-    uint64_t excl = block_exclusive_scan(p, lds, totals + (uint64_t)blockIdx.y * totals_stride + blockIdx.x);
-#pragma unroll
-    for (int k = 0; k < SCAN_E; k++) {
-        if (base + k < n) col[base + k] = gl::canon(excl);
-        excl = gl::mul(excl, e[k]);
-    }
-}
-
-// exclusive scan of m block totals per column by one workgroup
-__global__ __launch_bounds__(SCAN_T) void scan_totals_kernel(uint64_t *totals, uint64_t m, uint64_t totals_stride) {
-    __shared__ uint64_t lds[SCAN_T];
-    uint64_t *t = totals + (uint64_t)blockIdx.x * totals_stride;
-    uint64_t per = (m + SCAN_T - 1) / SCAN_T;
-    uint64_t lo = (uint64_t)threadIdx.x * per, hi = lo + per < m ? lo + per : m;
-    uint64_t p = 1;
-    for (uint64_t i = lo; i < hi; i++) p = gl::mul(p, t[i]);
-    uint64_t excl = block_exclusive_scan(p, lds, nullptr);
-    for (uint64_t i = lo; i < hi; i++) {
-        uint64_t x = t[i];
-        t[i] = excl;
-        excl = gl::mul(excl, x);
     }
 }
 

@@ -1,4 +1,5 @@
-// prove.hip — the prover's HOST logic in native code: gl_circuit_create / gl_prove.
+// prove.hip — the provers' HOST logic in native code: gl_circuit_create / gl_prove, and gl_stark_create / gl_stark_prove (starky's
+// prove(), at the end of this file) over the same commitments, transcript and FRI half.
 //
 // prove() (plonky2/src/plonk/prover.rs:40-233) from the full witness on, with PolynomialBatch::prove_openings
 // (plonky2/src/fri/oracle.rs:1047-1112), fri_proof (plonky2/src/fri/prover.rs:24-260), the Challenger
@@ -20,6 +21,7 @@
 #include "../../include/plonky2_hip.h"
 #include "gate_jit.h"
 #include "gl_field.h"
+#include "stark.h"
 
 namespace {
 
@@ -181,17 +183,42 @@ GlError keccak_hash_no_pad(const std::vector<uint64_t> &in, uint64_t out[4], voi
     return e;
 }
 
-// ---- the circuit object ---------------------------------------------------------------------------
-struct Circuit {
-    uint32_t degree_bits, num_wires, num_routed, num_constants, num_challenges, qdf, num_gate_constraints;
-    uint32_t rate_bits, cap_height, pow_bits, num_queries;
+// ---- what the commitments, the transcript and the FRI half of a proof need to know: shared by circuits and STARKs --------------
+struct ProverShape {
+    uint32_t degree_bits = 0, rate_bits = 0, cap_height = 0, pow_bits = 0, num_queries = 0;
     bool hiding = false;  // FriParams::hiding
     uint32_t hasher = GL_HASHER_POSEIDON;  // GenericConfig::Hasher: builds every Merkle tree; the Challenger stays Poseidon (plonk/config.rs:110-128)
     bool keccak() const { return hasher == GL_HASHER_KECCAK25; }
-    // how the transcript reads a hash of this circuit's trees: four field elements either way — a Poseidon HashOut as it lies, a
+    // how the transcript reads a hash of this prover's trees: four field elements either way — a Poseidon HashOut as it lies, a
     // Keccak digest slot through BytesHash<25>::to_vec (merkle.hip keccak_digest_chunk)
     GlObserveSrc hashes(const uint64_t *d_slots, uint64_t words) const { return GlObserveSrc{d_slots, words, keccak() ? GL_OBSERVE_KECCAK_DIGESTS : 0}; }
     std::vector<uint32_t> arity_bits;
+    mutable std::mutex pools_m;
+    mutable std::map<void *, Pool> pools;  // context -> the working buffers of this handle's proofs there, recycled from proof to proof
+    Pool *pool_of(void *ctx) const {
+        std::lock_guard<std::mutex> lock(pools_m);
+        return &pools[ctx];  // std::map: the address is stable
+    }
+    void set_fri(const GlFriParams &f) {
+        rate_bits = f.rate_bits, cap_height = f.cap_height, pow_bits = f.proof_of_work_bits, num_queries = f.num_query_rounds;
+        hiding = f.hiding != 0;
+        arity_bits.assign(f.reduction_arity_bits, f.reduction_arity_bits + f.num_reductions);
+    }
+    GlError trim() {
+        std::lock_guard<std::mutex> all(pools_m);
+        for (auto &cp : pools) {
+            Pool &pool = cp.second;
+            std::lock_guard<std::mutex> lock(pool.m);
+            for (auto &kv : pool.free_) TRY(gl_free(kv.second));
+            pool.free_.clear();
+        }
+        return ok();
+    }
+};
+
+// ---- the circuit object ---------------------------------------------------------------------------
+struct Circuit : ProverShape {
+    uint32_t num_wires, num_routed, num_constants, num_challenges, qdf, num_gate_constraints;
     uint64_t digest[4];  // HashOut, or one Keccak digest slot
     DevBuf k_is, sigmas;
     Batch cs;  // constants_sigmas_commitment
@@ -199,12 +226,6 @@ struct Circuit {
     DevBuf d_instrs, d_gates, d_imms;
     uint32_t num_gates = 0, num_selectors = 0;
     void *gate_kernel = nullptr;
-    mutable std::mutex pools_m;
-    mutable std::map<void *, Pool> pools;  // context -> the working buffers of this circuit's proofs there, recycled from proof to proof
-    Pool *pool_of(void *ctx) const {
-        std::lock_guard<std::mutex> lock(pools_m);
-        return &pools[ctx];  // std::map: the address is stable
-    }
     ~Circuit() {
         if (gate_kernel) gl_gate_kernel_destroy(gate_kernel);
     }
@@ -227,7 +248,7 @@ GlError canon_copy(uint64_t *d_dst, const uint64_t *d_src, uint64_t n, void *ctx
 }
 
 // d_salt: SALT_SIZE columns of n_ext caller-provided random elements in leaf order (a blinded commitment, prover.rs:84, 125, 174), or null
-GlError commit(Batch *b, DevBuf &&polys, bool from_values, uint32_t n_polys, const Circuit &c, void *ctx, const uint64_t *d_salt = nullptr,
+GlError commit(Batch *b, DevBuf &&polys, bool from_values, uint32_t n_polys, const ProverShape &c, void *ctx, const uint64_t *d_salt = nullptr,
               bool fetch_cap = true) {
     const uint64_t n_ext = 1ull << (c.degree_bits + c.rate_bits);
     const uint32_t salt = d_salt ? SALT_SIZE : 0;
@@ -292,6 +313,210 @@ struct Stages {
     }
 };
 
+// Asynchronous copies between device memory and the pool's page-locked staging, on the context's first stream.
+GlError copy_async(void *dst, const void *src, uint64_t bytes, bool to_host, void *ctx) {
+    if (!bytes) return ok();
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, *reinterpret_cast<hipStream_t *>(ctx));
+    if (e != hipSuccess) return fail(std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    return ok();
+}
+GlError stream_sync(void *ctx) {
+    const hipError_t e = hipStreamSynchronize(*reinterpret_cast<hipStream_t *>(ctx));
+    if (e != hipSuccess) return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return ok();
+}
+
+
+// ---- the FRI half of a proof: PolynomialBatch::prove_openings (fri/oracle.rs:1047-1112) over fri_proof (fri/prover.rs:24-260) ----
+// What a prover brings: its committed oracles, the two opening batches of its FriInstanceInfo as lists of coefficient columns,
+// the openings where gl_eval_polys_ext2 left them (observed as to_fri_openings orders them), and the transcript T. Everything small
+// lives in the prover's one device buffer D with its page-locked mirror H; the spans of this half are taken by fri_layout.
+struct Span {
+    uint64_t off = 0, words = 0;
+};
+struct SmallData {
+    uint64_t top = 0;
+    Span take(uint64_t words) {
+        Span sp{top, words};
+        top += (words + 1) & ~1ull;  // 16-byte granules
+        return sp;
+    }
+};
+struct FriShape {
+    uint64_t n_leaves;
+    uint32_t leaf_len, layers, shift;
+};
+struct FriLayout {
+    std::vector<FriShape> fs;
+    uint64_t final_len = 0;
+    uint32_t n_fri = 0, init_layers = 0;
+    Span alpha_fri_s, fri_betas, pow_w, resp_idx, fri_caps, final_s;
+    std::vector<Span> q_leaves, q_sib, s_leaves, s_sib;
+};
+struct FriBatch {  // FriBatchInfo: the polynomials opened at one point
+    E2 point;
+    std::vector<const uint64_t *> polys;  // device coefficient columns of length n
+};
+
+GlError fri_shapes(const ProverShape &c, FriLayout *L) {
+    const uint64_t n = 1ull << c.degree_bits;
+    L->n_fri = (uint32_t)c.arity_bits.size();
+    L->init_layers = c.degree_bits + c.rate_bits - c.cap_height;
+    L->fs.resize(L->n_fri);
+    uint64_t len = n;
+    uint32_t shift = 0;
+    for (uint32_t li = 0; li < L->n_fri; li++) {
+        const uint32_t ab = c.arity_bits[li];
+        L->fs[li].n_leaves = (len << c.rate_bits) >> ab, L->fs[li].leaf_len = 2u << ab;
+        if (L->fs[li].n_leaves < (1ull << c.cap_height)) return fail("FRI layer smaller than the Merkle cap");
+        uint32_t lg = 0;
+        while ((1ull << lg) < L->fs[li].n_leaves) lg++;
+        L->fs[li].layers = lg - c.cap_height;
+        shift += ab;
+        L->fs[li].shift = shift;
+        len >>= ab;
+    }
+    L->final_len = len;
+    return ok();
+}
+
+// after fri_shapes; leaf_len: of every oracle, salt included
+void fri_layout(const ProverShape &c, const std::vector<uint32_t> &leaf_len, SmallData *sd, FriLayout *L) {
+    const uint64_t cap_words = 4ull << c.cap_height, nq = c.num_queries;
+    L->alpha_fri_s = sd->take(2), L->fri_betas = sd->take(2ull * L->n_fri), L->pow_w = sd->take(1), L->resp_idx = sd->take(1 + nq);
+    L->fri_caps = sd->take(cap_words * L->n_fri), L->final_s = sd->take(2 * L->final_len);
+    for (uint32_t ll : leaf_len) L->q_leaves.push_back(sd->take(nq * ll)), L->q_sib.push_back(sd->take(nq * L->init_layers * 4));
+    for (uint32_t li = 0; li < L->n_fri; li++)
+        L->s_leaves.push_back(sd->take(nq * L->fs[li].leaf_len)), L->s_sib.push_back(sd->take(nq * L->fs[li].layers * 4));
+}
+
+// From the FRI alpha to the query openings; marks stages 6 (combine), 7 (commit phase), 8 (proof of work). The caller fetches
+// everything, synchronises, marks stage 9 and calls fri_check_pow / fri_write.
+GlError fri_prove(const ProverShape &c, const FriLayout &L, uint64_t *D, uint64_t *H, const Span &T, const std::vector<const Batch *> &oracles,
+                  const std::vector<GlObserveSrc> &opening_srcs, const std::vector<FriBatch> &batches, Stages &st, uint64_t *pow_witness, void *ctx) {
+    const uint64_t n = 1ull << c.degree_bits, n_ext = n << c.rate_bits, cap_words = 4ull << c.cap_height;
+    const uint32_t n_fri = L.n_fri, nq = c.num_queries;
+    const std::vector<FriShape> &fs = L.fs;
+    auto step = [&](std::initializer_list<GlObserveSrc> srcs, uint32_t n_out, const Span &out) {
+        return gl_challenger_step(D + T.off, srcs.begin(), (uint32_t)srcs.size(), n_out, n_out ? D + out.off : nullptr, 0, ctx);
+    };
+    TRY(gl_challenger_step(D + T.off, opening_srcs.data(), (uint32_t)opening_srcs.size(), 2, D + L.alpha_fri_s.off, 0, ctx));
+    TRY(copy_async(H + L.alpha_fri_s.off, D + L.alpha_fri_s.off, L.alpha_fri_s.words * 8, true, ctx));
+    TRY(stream_sync(ctx));
+    const E2 alpha{H[L.alpha_fri_s.off], H[L.alpha_fri_s.off + 1]};
+    DevBuf final_poly;  // planar [2][n]
+    TRY(final_poly.alloc(2 * n));
+    {
+        std::vector<const uint64_t *> ptrs;
+        for (const FriBatch &b : batches) ptrs.insert(ptrs.end(), b.polys.begin(), b.polys.end());
+        DevBuf d_ptrs, comp;
+        TRY(d_ptrs.alloc(ptrs.size()));
+        TRY(gl_memcpy_h2d(d_ptrs.p, ptrs.data(), ptrs.size() * 8, ctx));
+        TRY(comp.alloc(2 * n));
+        const uint64_t al[2] = {alpha.a, alpha.b};
+        uint64_t off = 0;
+        for (size_t b = 0; b < batches.size(); b++) {
+            const uint32_t m = (uint32_t)batches[b].polys.size();
+            TRY(gl_fri_reduce_polys_base(reinterpret_cast<const uint64_t *const *>(d_ptrs.p) + off, m, n, al, comp.p, ctx));
+            const E2 sc = e2_pow(alpha, m);  // alpha.shift_poly (util/reducing.rs:103-106)
+            const uint64_t pt[2] = {batches[b].point.a, batches[b].point.b}, scale[2] = {sc.a, sc.b};
+            TRY(gl_fri_divide_by_linear(comp.p, n, pt, scale, b != 0, final_poly.p, ctx));
+            off += m;
+        }
+        // d_ptrs / comp return to the pool here while their kernels may still be queued: stream order
+    }
+    TRY(st.mark(6));
+    // ---- fri_committed_trees (fri/prover.rs:77-120): no host synchronisation inside — the betas stay on the device ----
+    struct Layer {
+        DevBuf rows, digests, cap_d;
+    };
+    std::vector<Layer> layers(n_fri);
+    DevBuf final_coeffs_d;
+    {
+        DevBuf coeffs = std::move(final_poly), vals;
+        uint64_t len = n, shift = 7;
+        auto lde = [&](DevBuf *dst) -> GlError {
+            uint32_t lg = 0;
+            while ((1ull << lg) < len) lg++;
+            TRY(dst->alloc(2 * (len << c.rate_bits)));
+            return gl_coset_lde_batch(coeffs.p, dst->p, 2, lg, c.rate_bits, shift, len, len << c.rate_bits, ctx);
+        };
+        if (!layers.empty()) TRY(lde(&vals));
+        for (uint32_t li = 0; li < n_fri; li++) {
+            const uint32_t ab = c.arity_bits[li];
+            const uint64_t lde_len = len << c.rate_bits;
+            Layer &Ly = layers[li];
+            TRY(Ly.rows.alloc(2 * lde_len));
+            TRY(gl_ext2_interleave(vals.p, lde_len, Ly.rows.p, ctx));
+            TRY(Ly.digests.alloc(8 * (fs[li].n_leaves - (1ull << c.cap_height)) + 4));
+            TRY(Ly.cap_d.alloc(cap_words));
+            TRY(gl_merkle_tree_from_leaves_h(c.hasher, Ly.rows.p, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, Ly.digests.p, Ly.cap_d.p, ctx));
+            TRY(gl_memcpy_d2d(D + L.fri_caps.off + li * cap_words, Ly.cap_d.p, cap_words * 8, ctx));
+            TRY(step({c.hashes(Ly.cap_d.p, cap_words)}, 2, Span{L.fri_betas.off + 2ull * li, 2}));
+            DevBuf next;
+            TRY(next.alloc(2 * (len >> ab)));
+            TRY(gl_fri_fold_device(coeffs.p, len, ab, D + L.fri_betas.off + 2ull * li, next.p, ctx));
+            coeffs = std::move(next);  // the old coefficients return to the pool (stream order keeps them valid)
+            len >>= ab;
+            shift = glh::pow(shift, 1ull << ab);
+            if (li + 1 < n_fri) TRY(lde(&vals));
+        }
+        // observe_extension_elements(final_poly.coeffs) (fri/prover.rs:117): the two planes read interleaved
+        TRY(step({GlObserveSrc{coeffs.p, 2 * len, len}}, 0, Span{}));
+        final_coeffs_d = std::move(coeffs);
+    }
+    TRY(st.mark(7));
+    // ---- fri_proof_of_work (fri/prover.rs:122-171) ----
+    *pow_witness = 0;
+    TRY(gl_fri_proof_of_work_device(D + T.off, c.pow_bits, D + L.pow_w.off, pow_witness, ctx));  // F::order() has 64 bits: leading zeros of the u64 response
+    // observe the witness, draw the response, then the query indices (fri/prover.rs:163-170, 181-190)
+    TRY(step({GlObserveSrc{D + L.pow_w.off, 1, 0}}, 1 + nq, L.resp_idx));
+    TRY(st.mark(8));
+    // ---- fri_prover_query_rounds (fri/prover.rs:173-260): the indices never leave the device ----
+    const uint64_t *d_idx = D + L.resp_idx.off + 1;
+    for (size_t o = 0; o < oracles.size(); o++)  // salted leaves go into the proof whole (fri/prover.rs:203-210)
+        TRY(gl_merkle_open_batch_device(oracles[o]->lde.p, 1, n_ext, oracles[o]->leaf_len, n_ext, c.cap_height, oracles[o]->digests.p, d_idx, nq, 0,
+                                        D + L.q_leaves[o].off, D + L.q_sib[o].off, ctx));
+    for (uint32_t li = 0; li < n_fri; li++)
+        TRY(gl_merkle_open_batch_device(layers[li].rows.p, fs[li].leaf_len, 1, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, layers[li].digests.p,
+                                        d_idx, nq, fs[li].shift, D + L.s_leaves[li].off, D + L.s_sib[li].off, ctx));
+    return gl_memcpy_d2d(D + L.final_s.off, final_coeffs_d.p, 2 * L.final_len * 8, ctx);
+}
+
+GlError fri_check_pow(const ProverShape &c, const FriLayout &L, const uint64_t *H, uint64_t pow_witness) {
+    if (c.pow_bits && (H[L.resp_idx.off] >> (64 - c.pow_bits)) != 0) return fail("proof-of-work response does not have the required leading zeros");
+    if (H[L.pow_w.off] != pow_witness) return fail("proof-of-work witness changed between the search and the transcript");
+    return ok();
+}
+
+// write_fri_proof (util/serialization.rs:591-639)
+void fri_write(Bytes &out, const ProverShape &c, const FriLayout &L, const uint64_t *H, const std::vector<const Batch *> &oracles, uint64_t pow_witness) {
+    const uint64_t cap_words = 4ull << c.cap_height;
+    for (uint32_t li = 0; li < L.n_fri; li++) out.hashes(H + L.fri_caps.off + li * cap_words, cap_words / 4);
+    for (uint32_t q = 0; q < c.num_queries; q++) {
+        for (size_t o = 0; o < oracles.size(); o++) {
+            const uint32_t ll = oracles[o]->leaf_len;
+            out.fields(H + L.q_leaves[o].off + (uint64_t)q * ll, ll);
+            out.merkle_proof(H + L.q_sib[o].off + (uint64_t)q * L.init_layers * 4, L.init_layers);
+        }
+        for (uint32_t li = 0; li < L.n_fri; li++) {
+            out.fields(H + L.s_leaves[li].off + (uint64_t)q * L.fs[li].leaf_len, L.fs[li].leaf_len);
+            out.merkle_proof(H + L.s_sib[li].off + (uint64_t)q * L.fs[li].layers * 4, L.fs[li].layers);
+        }
+    }
+    for (uint64_t i = 0; i < L.final_len; i++) out.field(H[L.final_s.off + i]), out.field(H[L.final_s.off + L.final_len + i]);  // interleaved (a_i, b_i)
+    out.field(pow_witness);
+}
+
+GlError bytes_out(const Bytes &out, uint8_t **proof, uint64_t *proof_len) {
+    uint8_t *buf = static_cast<uint8_t *>(malloc(out.v.size() ? out.v.size() : 1));
+    if (!buf) return fail("out of memory");
+    memcpy(buf, out.v.data(), out.v.size());
+    *proof = buf;
+    *proof_len = out.v.size();
+    return ok();
+}
+
 }  // namespace
 
 extern "C" {
@@ -329,10 +554,7 @@ static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **ci
     c->degree_bits = d->degree_bits, c->num_wires = d->num_wires, c->num_routed = d->num_routed_wires;
     c->num_constants = d->num_constants, c->num_challenges = d->num_challenges, c->qdf = d->quotient_degree_factor;
     c->num_gate_constraints = d->num_gate_constraints;
-    c->rate_bits = d->fri.rate_bits, c->cap_height = d->fri.cap_height, c->pow_bits = d->fri.proof_of_work_bits;
-    c->num_queries = d->fri.num_query_rounds;
-    c->hiding = d->fri.hiding != 0;
-    c->arity_bits.assign(d->fri.reduction_arity_bits, d->fri.reduction_arity_bits + d->fri.num_reductions);
+    c->set_fri(d->fri);
     const uint64_t n = 1ull << c->degree_bits;
     auto bail = [&](GlError e) {
         delete c;
@@ -421,15 +643,7 @@ void gl_circuit_destroy(void *circuit) { delete static_cast<Circuit *>(circuit);
 
 GlError gl_circuit_trim(void *circuit) {
     if (!circuit) return fail("null pointer");
-    Circuit *c = static_cast<Circuit *>(circuit);
-    std::lock_guard<std::mutex> all(c->pools_m);
-    for (auto &cp : c->pools) {
-        Pool &pool = cp.second;
-        std::lock_guard<std::mutex> lock(pool.m);
-        for (auto &kv : pool.free_) TRY(gl_free(kv.second));
-        pool.free_.clear();
-    }
-    return ok();
+    return static_cast<Circuit *>(circuit)->trim();
 }
 
 GlError gl_circuit_info(const void *circuit, uint64_t h_digest[4], uint64_t *h_constants_sigmas_cap) {
@@ -441,19 +655,6 @@ GlError gl_circuit_info(const void *circuit, uint64_t h_digest[4], uint64_t *h_c
 }
 
 void gl_bytes_free(uint8_t *p) { free(p); }
-
-// Asynchronous copies between device memory and the pool's page-locked staging, on the context's first stream.
-static GlError copy_async(void *dst, const void *src, uint64_t bytes, bool to_host, void *ctx) {
-    if (!bytes) return ok();
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, *reinterpret_cast<hipStream_t *>(ctx));
-    if (e != hipSuccess) return fail(std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-    return ok();
-}
-static GlError stream_sync(void *ctx) {
-    const hipError_t e = hipStreamSynchronize(*reinterpret_cast<hipStream_t *>(ctx));
-    if (e != hipSuccess) return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return ok();
-}
 
 // The transcript of a proof lives on the device (gl_challenger_step): every observation reads its source where the producing kernel
 // left it (caps, openings, the final polynomial, the proof-of-work witness), the FRI betas, the query indices and the proof-of-work
@@ -469,59 +670,28 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     if (!c.hiding && d_salts) return fail("gl_prove_zk on a circuit whose FRI parameters are not hiding");
     Pool *pool = c.pool_of(ctx);
     PoolScope pool_scope(pool);  // every DevBuf below comes from / returns to the circuit's pool of this context
-    const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, nq = c.num_queries, npi = num_public_inputs;
+    const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, npi = num_public_inputs;
     const uint64_t n = 1ull << db, n_ext = n << c.rate_bits, cap_words = 4ull << c.cap_height;
     const uint32_t npp = num_partial_products(c.num_routed, qdf);
-    const uint32_t lg_ext = db + c.rate_bits, init_layers = lg_ext - c.cap_height, n_fri = (uint32_t)c.arity_bits.size();
     if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_PROVE_STAGES);
     Stages st(h_stage_ms, ctx);
 
     // ---- the small-data side of the proof: one device buffer, one page-locked mirror -------------------------------------------
     const uint32_t n_polys[4] = {c.num_constants + c.num_routed, c.num_wires, nch * (1 + npp), nch * qdf};
     const uint32_t salt = d_salts ? SALT_SIZE : 0;
-    const uint32_t leaf_len[4] = {n_polys[0], n_polys[1] + salt, n_polys[2] + salt, n_polys[3] + salt};
-    struct FriShape {
-        uint64_t n_leaves;
-        uint32_t leaf_len, layers, shift;
-    };
-    std::vector<FriShape> fs(n_fri);
-    uint64_t final_len = n;
-    {
-        uint64_t len = n;
-        uint32_t shift = 0;
-        for (uint32_t li = 0; li < n_fri; li++) {
-            const uint32_t ab = c.arity_bits[li];
-            fs[li].n_leaves = (len << c.rate_bits) >> ab, fs[li].leaf_len = 2u << ab;
-            if (fs[li].n_leaves < (1ull << c.cap_height)) return fail("FRI layer smaller than the Merkle cap");
-            uint32_t lg = 0;
-            while ((1ull << lg) < fs[li].n_leaves) lg++;
-            fs[li].layers = lg - c.cap_height;
-            shift += ab;
-            fs[li].shift = shift;
-            len >>= ab;
-        }
-        final_len = len;
-    }
-    struct Span {
-        uint64_t off = 0, words = 0;
-    };
-    uint64_t top = 0;
-    auto take = [&](uint64_t words) {
-        Span sp{top, words};
-        top += (words + 1) & ~1ull;  // 16-byte granules
-        return sp;
-    };
+    const std::vector<uint32_t> leaf_len = {n_polys[0], n_polys[1] + salt, n_polys[2] + salt, n_polys[3] + salt};
+    FriLayout L;
+    TRY(fri_shapes(c, &L));
+    SmallData sd;
+    auto take = [&](uint64_t words) { return sd.take(words); };
     const Span T = take(32), HP = take(32), hostin = take(4 + (uint64_t)npi);
     const Span fetch0 = take(0);  // from here on: what the host fetches
-    const Span pih_s = take(4), bg = take(2ull * nch), alphas_s = take(nch), zeta_s = take(2), alpha_fri_s = take(2), fri_betas = take(2ull * n_fri);
-    const Span pow_w = take(1), resp_idx = take(1 + (uint64_t)nq);
-    Span opens[4], caps[3], fri_caps = take(cap_words * n_fri), final_s = take(2 * final_len);
+    const Span pih_s = take(4), bg = take(2ull * nch), alphas_s = take(nch), zeta_s = take(2);
+    Span opens[4], caps[3];
     for (int o = 0; o < 4; o++) opens[o] = take(2ull * (o == 2 ? 2 : 1) * n_polys[o]);
     for (int o = 0; o < 3; o++) caps[o] = take(cap_words);
-    Span q_leaves[4], q_sib[4];
-    for (int o = 0; o < 4; o++) q_leaves[o] = take((uint64_t)nq * leaf_len[o]), q_sib[o] = take((uint64_t)nq * init_layers * 4);
-    std::vector<Span> s_leaves(n_fri), s_sib(n_fri);
-    for (uint32_t li = 0; li < n_fri; li++) s_leaves[li] = take((uint64_t)nq * fs[li].leaf_len), s_sib[li] = take((uint64_t)nq * fs[li].layers * 4);
+    fri_layout(c, leaf_len, &sd, &L);
+    const uint64_t top = sd.top;
     DevBuf small;
     TRY(small.alloc(top));
     uint64_t *const D = small.p;
@@ -637,107 +807,31 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
             TRY(gl_eval_polys_ext2(oracles[o]->coeffs.p, oracles[o]->n_polys, db, n, pts, o == 2 ? 2 : 1, D + opens[o].off, ctx));
     }
     TRY(st.mark(5));
-    // to_fri_openings (proof.rs:336-356): [constants, sigmas, wires, zs, partial products, quotient], then zs_next; then the FRI alpha
-    // ---- PolynomialBatch::prove_openings (fri/oracle.rs:1047-1112) ----
-    TRY(step({GlObserveSrc{D + opens[0].off, 2ull * n_polys[0], 0}, GlObserveSrc{D + opens[1].off, 2ull * n_polys[1], 0},
-              GlObserveSrc{D + opens[2].off, 2ull * n_polys[2], 0}, GlObserveSrc{D + opens[3].off, 2ull * n_polys[3], 0},
-              GlObserveSrc{D + opens[2].off + 2ull * n_polys[2], 2ull * nch, 0}},
-             2, alpha_fri_s));
-    TRY(fetch(alpha_fri_s));
-    TRY(stream_sync(ctx));
-    const E2 alpha{H[alpha_fri_s.off], H[alpha_fri_s.off + 1]};
-    DevBuf final_poly;  // planar [2][n]
-    TRY(final_poly.alloc(2 * n));
-    {
-        // batch 0: every polynomial of the four oracles at zeta; batch 1: the Zs at g*zeta (circuit_data.rs:351-371)
-        std::vector<const uint64_t *> ptrs;
-        for (int o = 0; o < 4; o++)
-            for (uint32_t k = 0; k < oracles[o]->n_polys; k++) ptrs.push_back(oracles[o]->coeffs.p + (uint64_t)k * n);
-        const uint32_t m0 = (uint32_t)ptrs.size();
-        for (uint32_t k = 0; k < nch; k++) ptrs.push_back(zs.coeffs.p + (uint64_t)k * n);
-        DevBuf d_ptrs, comp;
-        TRY(d_ptrs.alloc(ptrs.size()));
-        TRY(gl_memcpy_h2d(d_ptrs.p, ptrs.data(), ptrs.size() * 8, ctx));
-        TRY(comp.alloc(2 * n));
-        const uint64_t al[2] = {alpha.a, alpha.b};
-        const struct {
-            uint32_t off, m;
-            E2 point;
-        } batches[2] = {{0, m0, zeta}, {m0, nch, g_zeta}};
-        for (int b = 0; b < 2; b++) {
-            TRY(gl_fri_reduce_polys_base(reinterpret_cast<const uint64_t *const *>(d_ptrs.p) + batches[b].off, batches[b].m, n, al, comp.p,
-                                         ctx));
-            const E2 sc = e2_pow(alpha, batches[b].m);  // alpha.shift_poly (util/reducing.rs:103-106)
-            const uint64_t pt[2] = {batches[b].point.a, batches[b].point.b}, scale[2] = {sc.a, sc.b};
-            TRY(gl_fri_divide_by_linear(comp.p, n, pt, scale, b != 0, final_poly.p, ctx));
-        }
-        // d_ptrs / comp return to the pool here while their kernels may still be queued: stream order
-    }
-    TRY(st.mark(6));
-    // ---- fri_committed_trees (fri/prover.rs:77-120): no host synchronisation inside — the betas stay on the device ----
-    struct Layer {
-        DevBuf rows, digests, cap_d;
-    };
-    std::vector<Layer> layers(n_fri);
-    DevBuf final_coeffs_d;
-    {
-        DevBuf coeffs = std::move(final_poly), vals;
-        uint64_t len = n, shift = 7;
-        auto lde = [&](DevBuf *dst) -> GlError {
-            uint32_t lg = 0;
-            while ((1ull << lg) < len) lg++;
-            TRY(dst->alloc(2 * (len << c.rate_bits)));
-            return gl_coset_lde_batch(coeffs.p, dst->p, 2, lg, c.rate_bits, shift, len, len << c.rate_bits, ctx);
-        };
-        if (!layers.empty()) TRY(lde(&vals));
-        for (uint32_t li = 0; li < n_fri; li++) {
-            const uint32_t ab = c.arity_bits[li];
-            const uint64_t lde_len = len << c.rate_bits;
-            Layer &L = layers[li];
-            TRY(L.rows.alloc(2 * lde_len));
-            TRY(gl_ext2_interleave(vals.p, lde_len, L.rows.p, ctx));
-            TRY(L.digests.alloc(8 * (fs[li].n_leaves - (1ull << c.cap_height)) + 4));
-            TRY(L.cap_d.alloc(cap_words));
-            TRY(gl_merkle_tree_from_leaves_h(c.hasher, L.rows.p, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, L.digests.p, L.cap_d.p, ctx));
-            TRY(gl_memcpy_d2d(D + fri_caps.off + li * cap_words, L.cap_d.p, cap_words * 8, ctx));
-            TRY(step({c.hashes(L.cap_d.p, cap_words)}, 2, Span{fri_betas.off + 2ull * li, 2}));
-            DevBuf next;
-            TRY(next.alloc(2 * (len >> ab)));
-            TRY(gl_fri_fold_device(coeffs.p, len, ab, D + fri_betas.off + 2ull * li, next.p, ctx));
-            coeffs = std::move(next);  // the old coefficients return to the pool (stream order keeps them valid)
-            len >>= ab;
-            shift = glh::pow(shift, 1ull << ab);
-            if (li + 1 < n_fri) TRY(lde(&vals));
-        }
-        // observe_extension_elements(final_poly.coeffs) (fri/prover.rs:117): the two planes read interleaved
-        TRY(step({GlObserveSrc{coeffs.p, 2 * len, len}}, 0, Span{}));
-        final_coeffs_d = std::move(coeffs);
-    }
-    TRY(st.mark(7));
-    // ---- fri_proof_of_work (fri/prover.rs:122-171) ----
+    // to_fri_openings (proof.rs:336-356): [constants, sigmas, wires, zs, partial products, quotient], then zs_next; then
+    // PolynomialBatch::prove_openings: batch 0 is every polynomial of the four oracles at zeta, batch 1 the Zs at g*zeta
+    // (circuit_data.rs:351-371)
+    const std::vector<const Batch *> oracle_list(oracles, oracles + 4);
     uint64_t pow_witness = 0;
-    TRY(gl_fri_proof_of_work_device(D + T.off, c.pow_bits, D + pow_w.off, &pow_witness, ctx));  // F::order() has 64 bits: leading zeros of the u64 response
-    // observe the witness, draw the response, then the query indices (fri/prover.rs:163-170, 181-190)
-    TRY(step({GlObserveSrc{D + pow_w.off, 1, 0}}, 1 + nq, resp_idx));
-    TRY(st.mark(8));
-    // ---- fri_prover_query_rounds (fri/prover.rs:173-260): the indices never leave the device ----
-    const uint64_t *d_idx = D + resp_idx.off + 1;
-    for (int o = 0; o < 4; o++)  // salted leaves go into the proof whole (fri/prover.rs:203-210)
-        TRY(gl_merkle_open_batch_device(oracles[o]->lde.p, 1, n_ext, oracles[o]->leaf_len, n_ext, c.cap_height, oracles[o]->digests.p, d_idx, nq, 0,
-                                        D + q_leaves[o].off, D + q_sib[o].off, ctx));
-    for (uint32_t li = 0; li < n_fri; li++)
-        TRY(gl_merkle_open_batch_device(layers[li].rows.p, fs[li].leaf_len, 1, fs[li].leaf_len, fs[li].n_leaves, c.cap_height, layers[li].digests.p,
-                                        d_idx, nq, fs[li].shift, D + s_leaves[li].off, D + s_sib[li].off, ctx));
+    {
+        std::vector<FriBatch> batches(2);
+        batches[0].point = zeta, batches[1].point = g_zeta;
+        for (int o = 0; o < 4; o++)
+            for (uint32_t k = 0; k < oracles[o]->n_polys; k++) batches[0].polys.push_back(oracles[o]->coeffs.p + (uint64_t)k * n);
+        for (uint32_t k = 0; k < nch; k++) batches[1].polys.push_back(zs.coeffs.p + (uint64_t)k * n);
+        const std::vector<GlObserveSrc> opening_srcs = {
+            GlObserveSrc{D + opens[0].off, 2ull * n_polys[0], 0}, GlObserveSrc{D + opens[1].off, 2ull * n_polys[1], 0},
+            GlObserveSrc{D + opens[2].off, 2ull * n_polys[2], 0}, GlObserveSrc{D + opens[3].off, 2ull * n_polys[3], 0},
+            GlObserveSrc{D + opens[2].off + 2ull * n_polys[2], 2ull * nch, 0}};
+        TRY(fri_prove(c, L, D, H, T, oracle_list, opening_srcs, batches, st, &pow_witness, ctx));
+    }
     // everything the proof consists of, in one go
     TRY(gl_memcpy_d2d(D + caps[0].off, wires.cap_d.p, cap_words * 8, ctx));
     TRY(gl_memcpy_d2d(D + caps[1].off, zs.cap_d.p, cap_words * 8, ctx));
     TRY(gl_memcpy_d2d(D + caps[2].off, quot.cap_d.p, cap_words * 8, ctx));
-    TRY(gl_memcpy_d2d(D + final_s.off, final_coeffs_d.p, 2 * final_len * 8, ctx));
     TRY(fetch(Span{fetch0.off, top - fetch0.off}));
     TRY(gl_ctx_synchronize(ctx));
     TRY(st.mark(9));
-    if (c.pow_bits && (H[resp_idx.off] >> (64 - c.pow_bits)) != 0) return fail("proof-of-work response does not have the required leading zeros");
-    if (H[pow_w.off] != pow_witness) return fail("proof-of-work witness changed between the search and the transcript");
+    TRY(fri_check_pow(c, L, H, pow_witness));
     // ---- write_proof_with_public_inputs (util/serialization.rs:641-689) ----
     Bytes out;
     out.keccak = c.keccak();
@@ -750,25 +844,9 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     out.fields(ev[2] + 2ull * n_polys[2], 2ull * nch);                      // plonk_zs_next
     out.fields(ev[2] + 2ull * nch, 2ull * n_polys[2] - 2ull * nch);         // partial_products
     out.fields(ev[3], 2ull * n_polys[3]);                                   // quotient_polys
-    for (uint32_t li = 0; li < n_fri; li++) out.hashes(H + fri_caps.off + li * cap_words, cap_words / 4);
-    for (uint32_t q = 0; q < nq; q++) {
-        for (int o = 0; o < 4; o++) {
-            out.fields(H + q_leaves[o].off + (uint64_t)q * leaf_len[o], leaf_len[o]);
-            out.merkle_proof(H + q_sib[o].off + (uint64_t)q * init_layers * 4, init_layers);
-        }
-        for (uint32_t li = 0; li < n_fri; li++) {
-            out.fields(H + s_leaves[li].off + (uint64_t)q * fs[li].leaf_len, fs[li].leaf_len);
-            out.merkle_proof(H + s_sib[li].off + (uint64_t)q * fs[li].layers * 4, fs[li].layers);
-        }
-    }
-    for (uint64_t i = 0; i < final_len; i++) out.field(H[final_s.off + i]), out.field(H[final_s.off + final_len + i]);  // interleaved (a_i, b_i)
-    out.field(pow_witness);
+    fri_write(out, c, L, H, oracle_list, pow_witness);
     out.fields(h_public_inputs, num_public_inputs);
-    uint8_t *buf = static_cast<uint8_t *>(malloc(out.v.size() ? out.v.size() : 1));
-    if (!buf) return fail("out of memory");
-    memcpy(buf, out.v.data(), out.v.size());
-    *proof = buf;
-    *proof_len = out.v.size();
+    TRY(bytes_out(out, proof, proof_len));
     return st.mark(10);
 }
 
@@ -823,6 +901,332 @@ GlError gl_prove_zk(const void *circuit, const uint64_t *d_wires, const uint64_t
                     const uint64_t *d_salts, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms, void *ctx) {
     if (!d_salts) return fail("gl_prove_zk: null salt columns");
     return prove_impl(circuit, d_wires, h_public_inputs, num_public_inputs, d_salts, proof, proof_len, h_stage_ms, ctx);
+}
+
+}  // extern "C"
+
+// ---- STARKs: gl_stark_create / gl_stark_prove = starky's prove() (starky/src/prover.rs:32-195) --------------------------------------
+namespace {
+
+struct Stark : ProverShape {
+    uint32_t num_columns = 0, num_public_inputs = 0, num_challenges = 0, qdf = 0, qdb = 0, num_instrs = 0, num_pairs = 0, num_zs = 0;
+    DevBuf d_instrs, d_imms, d_column_pairs, d_pair_bounds;
+    plonky2_hip::StarkPairsDev pairs() const {
+        plonky2_hip::StarkPairsDev p;
+        p.column_pairs = reinterpret_cast<const uint32_t *>(d_column_pairs.p), p.pair_bounds = reinterpret_cast<const uint32_t *>(d_pair_bounds.p);
+        p.num_pairs = num_pairs;
+        return p;
+    }
+};
+
+GlError hip_fail(hipError_t e, const char *what) { return GlError{(int)e, strdup((std::string(what) + ": " + hipGetErrorString(e)).c_str())}; }
+
+// the quotient values of one trace, then their coset_ifft (prover.rs:314-318)
+GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride, const uint64_t *h_alphas,
+                       const uint64_t *h_challenges, const uint64_t *d_public_inputs, uint64_t *d_out, void *ctx) {
+    const plonky2_hip::NttTables *tb;
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    plonky2_hip::StarkQuotientArgs a = {};
+    a.instrs = reinterpret_cast<const uint16_t *>(s.d_instrs.p), a.num_instrs = s.num_instrs, a.imms = s.d_imms.p, a.public_inputs = d_public_inputs;
+    a.trace_lde = d_trace_lde, a.zs_lde = d_zs_lde, a.column_stride = column_stride, a.pairs = s.pairs();
+    a.alphas = h_alphas, a.challenges = h_challenges;
+    a.num_challenges = s.num_challenges, a.qdf = s.qdf, a.degree_bits = s.degree_bits, a.rate_bits = s.rate_bits;
+    const hipError_t e = plonky2_hip::stark_quotient_values(*tb, a, d_out, *reinterpret_cast<hipStream_t *>(ctx));
+    if (e == hipErrorInvalidValue) return fail("inconsistent arguments of the STARK quotient (column_stride / challenges / sizes)");
+    if (e != hipSuccess) return hip_fail(e, "stark_quotient_values");
+    const uint32_t log_size = s.degree_bits + s.qdb;
+    return gl_coset_ntt_batch(d_out, s.num_challenges, log_size, 1ull << log_size, 7, 1, ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, void *ctx) {
+    if (!d || !stark || !ctx || !d->h_instrs || (d->num_immediates && !d->h_immediates) || (d->fri.num_reductions && !d->fri.reduction_arity_bits) ||
+        (d->num_pairs && (!d->h_column_pairs || !d->h_pair_bounds)))
+        return fail("null pointer");
+    if (d->struct_size != sizeof(GlStarkDesc))
+        return fail("GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+    if (hasher != GL_HASHER_POSEIDON && hasher != GL_HASHER_KECCAK25) return fail("unknown hasher");
+    if (d->fri.hiding) return fail("a STARK's FRI parameters are not hiding (starky: fri_params(degree_bits, false))");
+    if (d->degree_bits == 0 || d->degree_bits + d->fri.rate_bits > 24 || d->num_columns == 0 || d->num_columns > 65535 || d->num_public_inputs > 65535 ||
+        d->num_challenges == 0 || d->num_challenges > plonky2_hip::STARK_MAX_CHALLENGES || d->constraint_degree == 0)
+        return fail("bad STARK shape (1 <= degree_bits, degree_bits + rate_bits <= 24, 1 <= num_columns, 1 <= num_challenges <= 4, 1 <= constraint_degree)");
+    const uint32_t qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;  // stark.rs:79-81
+    uint32_t qdb = 0;
+    while ((1u << qdb) < qdf) qdb++;
+    if (qdf > plonky2_hip::STARK_MAX_QDF) return fail("quotient_degree_factor > 16");
+    if (qdb > d->fri.rate_bits) return fail("Having constraints of degree higher than the rate is not supported yet. (log2_ceil(quotient_degree_factor) > rate_bits, prover.rs:223-226)");
+    uint32_t total_arity = 0;
+    for (uint32_t li = 0; li < d->fri.num_reductions; li++) total_arity += d->fri.reduction_arity_bits[li];
+    if (d->fri.cap_height > d->degree_bits + d->fri.rate_bits || total_arity > d->degree_bits + d->fri.rate_bits - d->fri.cap_height || total_arity > d->degree_bits)
+        return fail("FRI total reduction arity is too large.");
+    uint32_t num_column_pairs = 0;
+    if (d->num_pairs) {
+        if (d->h_pair_bounds[0] != 0) return fail("h_pair_bounds must start at 0");
+        for (uint32_t p = 0; p < d->num_pairs; p++)
+            if (d->h_pair_bounds[p + 1] < d->h_pair_bounds[p]) return fail("h_pair_bounds must not decrease");
+        num_column_pairs = d->h_pair_bounds[d->num_pairs];
+        for (uint32_t k = 0; k < 2 * num_column_pairs; k++)
+            if (d->h_column_pairs[k] >= d->num_columns) return fail("permutation pair: column out of range");
+    }
+    const uint32_t num_zs = d->num_pairs ? plonky2_hip::stark_num_zs(d->num_pairs, d->num_challenges, qdf) : 0;
+    {
+        std::string verr;
+        if (!plonky2_hip::stark_program_validate(reinterpret_cast<const uint16_t *>(d->h_instrs), d->num_instrs, d->h_immediates, d->num_immediates,
+                                                 d->num_columns, d->num_public_inputs, &verr))
+            return fail(verr);
+    }
+    if (hasher == GL_HASHER_KECCAK25) {  // as gl_circuit_create_h: KeccakHash<25>::hash_or_noop panics on a leaf of exactly four elements
+        const struct {
+            const char *name;
+            uint32_t leaf_len;
+        } commitments[3] = {{"trace", d->num_columns}, {"permutation Zs", num_zs}, {"quotient", d->num_challenges * qdf}};
+        for (const auto &cm : commitments)
+            if (cm.leaf_len == 4)
+                return fail(std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
+                            " commitment have 4");
+        for (uint32_t li = 0; li < d->fri.num_reductions; li++)
+            if (d->fri.reduction_arity_bits[li] == 1)
+                return fail("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
+                            " has arity_bits = 1: its leaves are 2 extension elements");
+    }
+    const plonky2_hip::NttTables *tb;  // makes the context's device current before the first allocation
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    Stark *s = new Stark();
+    s->hasher = hasher;
+    s->degree_bits = d->degree_bits, s->num_columns = d->num_columns, s->num_public_inputs = d->num_public_inputs;
+    s->num_challenges = d->num_challenges, s->qdf = qdf, s->qdb = qdb, s->num_instrs = d->num_instrs, s->num_pairs = d->num_pairs, s->num_zs = num_zs;
+    s->set_fri(d->fri);
+    auto bail = [&](GlError e) {
+        delete s;
+        return e;
+    };
+#define STRY(expr)                         \
+    do {                                   \
+        GlError _e = (expr);               \
+        if (_e.code != 0) return bail(_e); \
+    } while (0)
+    STRY(s->d_instrs.alloc(d->num_instrs));  // 8 bytes per GlGateInstr
+    STRY(gl_memcpy_h2d(s->d_instrs.p, d->h_instrs, 8ull * d->num_instrs, ctx));
+    if (d->num_immediates) {
+        std::vector<uint64_t> imms(d->h_immediates, d->h_immediates + d->num_immediates);
+        for (uint64_t &v : imms) v %= P;
+        STRY(s->d_imms.alloc(imms.size()));
+        STRY(gl_memcpy_h2d(s->d_imms.p, imms.data(), 8ull * imms.size(), ctx));
+    }
+    if (d->num_pairs) {
+        STRY(s->d_column_pairs.alloc(num_column_pairs ? num_column_pairs : 1));  // two u32 per column pair
+        STRY(gl_memcpy_h2d(s->d_column_pairs.p, d->h_column_pairs, 8ull * num_column_pairs, ctx));
+        STRY(s->d_pair_bounds.alloc((d->num_pairs + 2) / 2));
+        STRY(gl_memcpy_h2d(s->d_pair_bounds.p, d->h_pair_bounds, 4ull * (d->num_pairs + 1), ctx));
+    }
+    STRY(gl_ctx_synchronize(ctx));
+#undef STRY
+    *stark = s;
+    return ok();
+}
+
+void gl_stark_destroy(void *stark) { delete static_cast<Stark *>(stark); }
+
+GlError gl_stark_trim(void *stark) {
+    if (!stark) return fail("null pointer");
+    return static_cast<Stark *>(stark)->trim();
+}
+
+GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
+                                void *ctx) {
+    if (!stark || !d_trace || !h_challenges || !d_zs || !ctx) return fail("null pointer");
+    const Stark &s = *static_cast<const Stark *>(stark);
+    if (!s.num_pairs) return fail("the STARK has no permutation pairs");
+    if (trace_stride < (1ull << s.degree_bits)) return fail("trace_stride smaller than the column length");
+    const plonky2_hip::NttTables *tb;
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    const hipError_t e = plonky2_hip::stark_permutation_zs(*tb, d_trace, trace_stride, s.pairs(), h_challenges, s.num_challenges, s.qdf, s.degree_bits, d_zs,
+                                                           *reinterpret_cast<hipStream_t *>(ctx));
+    if (e != hipSuccess) return hip_fail(e, "stark_permutation_zs");
+    return ok();
+}
+
+GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
+                                const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
+                                uint64_t *d_quotient_polys, void *ctx) {
+    if (!stark || !d_trace_lde || !h_alphas || !d_quotient_polys || !ctx) return fail("null pointer");
+    const Stark &s = *static_cast<const Stark *>(stark);
+    if (s.num_pairs && (!d_zs_lde || !h_challenges)) return fail("the STARK has permutation pairs: d_zs_lde and h_challenges are needed");
+    if (s.num_public_inputs && !h_public_inputs) return fail("null public inputs");
+    if (column_stride < (1ull << (s.degree_bits + s.rate_bits))) return fail("column_stride smaller than the LDE's column length n << rate_bits");
+    const plonky2_hip::NttTables *tb;  // the context's device becomes current
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    DevBuf pis;
+    TRY(pis.alloc(s.num_public_inputs));
+    std::vector<uint64_t> h_pis(s.num_public_inputs);
+    for (uint32_t i = 0; i < s.num_public_inputs; i++) h_pis[i] = h_public_inputs[i] % P;
+    TRY(gl_memcpy_h2d(pis.p, h_pis.data(), 8ull * h_pis.size(), ctx));
+    TRY(stark_quotient(s, d_trace_lde, d_zs_lde, column_stride, h_alphas, h_challenges, pis.p, d_quotient_polys, ctx));
+    return gl_ctx_synchronize(ctx);  // pis is freed on return
+}
+
+GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_t *h_public_inputs, uint8_t **proof, uint64_t *proof_len,
+                       double *h_stage_ms, void *ctx) {
+    if (!stark || !d_trace || !proof || !proof_len || !ctx) return fail("null pointer");
+    const Stark &c = *static_cast<const Stark *>(stark);
+    if (c.num_public_inputs && !h_public_inputs) return fail("null public inputs");
+    {  // the context's device is current from here on, whatever the calling thread had: every allocation below follows it
+        const plonky2_hip::NttTables *tb;
+        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    }
+    Pool *pool = c.pool_of(ctx);
+    PoolScope pool_scope(pool);  // every DevBuf below comes from / returns to the handle's pool of this context
+    const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, qdb = c.qdb, npi = c.num_public_inputs, nz = c.num_zs;
+    const uint64_t n = 1ull << db, n_ext = n << c.rate_bits, cap_words = 4ull << c.cap_height;
+    const bool perm = c.num_pairs != 0;
+    if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_STARK_STAGES);
+    Stages st(h_stage_ms, ctx);
+
+    // ---- the small-data side of the proof: one device buffer, one page-locked mirror ----
+    // oracles: trace, [Zs], quotient (stark.rs:94-119)
+    const uint32_t n_quot = nch * qdf;
+    std::vector<uint32_t> leaf_len = {c.num_columns};
+    if (perm) leaf_len.push_back(nz);
+    leaf_len.push_back(n_quot);
+    FriLayout L;
+    TRY(fri_shapes(c, &L));
+    SmallData sd;
+    const Span T = sd.take(32), hostin = sd.take(npi);
+    const Span fetch0 = sd.take(0);  // from here on: what the host fetches
+    const Span perm_s = sd.take(perm ? 2ull * qdf * nch : 0), alphas_s = sd.take(nch), zeta_s = sd.take(2);
+    // openings at zeta and g * zeta: [2][n_polys] extension elements for the trace and the Zs, [1][n_polys] for the quotient
+    const Span open_trace = sd.take(4ull * c.num_columns), open_zs = sd.take(4ull * nz), open_quot = sd.take(2ull * n_quot);
+    const Span cap_trace = sd.take(cap_words), cap_zs = sd.take(perm ? cap_words : 0), cap_quot = sd.take(cap_words);
+    fri_layout(c, leaf_len, &sd, &L);
+    const uint64_t top = sd.top;
+    DevBuf small;
+    TRY(small.alloc(top));
+    uint64_t *const D = small.p;
+    uint64_t *H = nullptr;
+    TRY(pool->staging(top, &H));
+    auto fetch = [&](const Span &sp) { return copy_async(H + sp.off, D + sp.off, sp.words * 8, true, ctx); };
+    auto step = [&](std::initializer_list<GlObserveSrc> srcs, uint32_t n_out, const Span &out, uint32_t flags = 0) {
+        return gl_challenger_step(D + T.off, srcs.begin(), (uint32_t)srcs.size(), n_out, n_out ? D + out.off : nullptr, flags, ctx);
+    };
+    for (uint32_t i = 0; i < npi; i++) H[hostin.off + i] = h_public_inputs[i] % P;
+    TRY(copy_async(D + hostin.off, H + hostin.off, hostin.words * 8, false, ctx));
+
+    // trace commitment (prover.rs:57-70); the caller's trace stays intact
+    Batch trace;
+    {
+        DevBuf w;
+        TRY(w.alloc((uint64_t)c.num_columns * n));
+        TRY(gl_memcpy_d2d(w.p, d_trace, 8ull * c.num_columns * n, ctx));
+        TRY(commit(&trace, std::move(w), true, c.num_columns, c, ctx, nullptr, false));
+    }
+    TRY(st.mark(0));
+    // a fresh Challenger observes the trace cap (prover.rs:72-74), nothing else
+    Batch zs;
+    std::vector<uint64_t> perm_challenges;
+    if (perm) {
+        // get_n_permutation_challenge_sets (permutation.rs:153-179): qdf sets of num_challenges (beta, gamma) draws
+        TRY(step({c.hashes(trace.cap_d.p, cap_words)}, 2 * qdf * nch, perm_s, GL_CHALLENGER_RESET));
+        TRY(fetch(perm_s));
+        TRY(stream_sync(ctx));
+        perm_challenges.assign(H + perm_s.off, H + perm_s.off + 2ull * qdf * nch);
+        DevBuf z;
+        TRY(z.alloc((uint64_t)nz * n));
+        TRY(gl_stark_permutation_zs(stark, d_trace, n, perm_challenges.data(), z.p, ctx));
+        TRY(st.mark(1));
+        TRY(commit(&zs, std::move(z), true, nz, c, ctx, nullptr, false));
+        TRY(st.mark(2));
+        TRY(step({c.hashes(zs.cap_d.p, cap_words)}, nch, alphas_s));
+    } else {
+        TRY(step({c.hashes(trace.cap_d.p, cap_words)}, nch, alphas_s, GL_CHALLENGER_RESET));
+    }
+    TRY(fetch(alphas_s));
+    TRY(stream_sync(ctx));
+    const std::vector<uint64_t> alphas(H + alphas_s.off, H + alphas_s.off + nch);
+    // quotient polynomials (prover.rs:115-123)
+    DevBuf quotient;
+    TRY(quotient.alloc((uint64_t)nch << (db + qdb)));
+    TRY(stark_quotient(c, trace.lde.p, perm ? zs.lde.p : nullptr, n_ext, alphas.data(), perm ? perm_challenges.data() : nullptr, D + hostin.off,
+                       quotient.p, ctx));
+    TRY(st.mark(3));
+    // trim_to_len(degree * qdf) and the split into degree-n chunks (prover.rs:124-133), committed from coefficients. Of the
+    // n << qdb coefficients those from qdf * n on must vanish: there are some only when qdf is no power of two.
+    Batch quot;
+    {
+        DevBuf chunks;
+        if (qdf == (1u << qdb)) {
+            chunks = std::move(quotient);  // [nch][n << qdb] read flat is [nch * qdf][n]
+        } else {
+            TRY(chunks.alloc((uint64_t)n_quot * n));
+            std::vector<uint64_t> tail((n << qdb) - (uint64_t)qdf * n);
+            for (uint32_t k = 0; k < nch; k++) {
+                TRY(gl_memcpy_d2h(tail.data(), quotient.p + ((uint64_t)k << (db + qdb)) + (uint64_t)qdf * n, tail.size() * 8, ctx));
+                for (uint64_t t : tail)
+                    if (t) return fail("Quotient has failed, the vanishing polynomial is not divisible by Z_H");
+                TRY(gl_memcpy_d2d(chunks.p + (uint64_t)k * qdf * n, quotient.p + ((uint64_t)k << (db + qdb)), 8ull * qdf * n, ctx));
+            }
+        }
+        TRY(commit(&quot, std::move(chunks), false, n_quot, c, ctx, nullptr, false));
+    }
+    TRY(st.mark(4));
+    TRY(step({c.hashes(quot.cap_d.p, cap_words)}, 2, zeta_s));
+    TRY(fetch(zeta_s));
+    TRY(stream_sync(ctx));
+    const E2 zeta{H[zeta_s.off], H[zeta_s.off + 1]};
+    if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail("Opening point is in the subgroup.");
+    const uint64_t g = glh::root_of_unity(db);
+    const E2 g_zeta = e2_mul(E2{g, 0}, zeta);
+    // StarkOpeningSet::new (proof.rs:138-159): trace and Zs at zeta and g * zeta, the quotient at zeta
+    {
+        const uint64_t pts[4] = {zeta.a, zeta.b, g_zeta.a, g_zeta.b};
+        TRY(gl_eval_polys_ext2(trace.coeffs.p, c.num_columns, db, n, pts, 2, D + open_trace.off, ctx));
+        if (perm) TRY(gl_eval_polys_ext2(zs.coeffs.p, nz, db, n, pts, 2, D + open_zs.off, ctx));
+        TRY(gl_eval_polys_ext2(quot.coeffs.p, n_quot, db, n, pts, 1, D + open_quot.off, ctx));
+    }
+    TRY(st.mark(5));
+    // to_fri_openings (proof.rs:161-182): [local_values, permutation_zs, quotient_polys], then [next_values, permutation_zs_next];
+    // the instance of stark.rs:88-137: batch 0 everything at zeta, batch 1 trace then Zs at g * zeta
+    std::vector<const Batch *> oracles = {&trace};
+    if (perm) oracles.push_back(&zs);
+    oracles.push_back(&quot);
+    uint64_t pow_witness = 0;
+    {
+        std::vector<FriBatch> batches(2);
+        batches[0].point = zeta, batches[1].point = g_zeta;
+        for (const Batch *o : oracles)
+            for (uint32_t k = 0; k < o->n_polys; k++) batches[0].polys.push_back(o->coeffs.p + (uint64_t)k * n);
+        for (size_t o = 0; o + 1 < oracles.size(); o++)
+            for (uint32_t k = 0; k < oracles[o]->n_polys; k++) batches[1].polys.push_back(oracles[o]->coeffs.p + (uint64_t)k * n);
+        std::vector<GlObserveSrc> srcs = {GlObserveSrc{D + open_trace.off, 2ull * c.num_columns, 0}};
+        if (perm) srcs.push_back(GlObserveSrc{D + open_zs.off, 2ull * nz, 0});
+        srcs.push_back(GlObserveSrc{D + open_quot.off, 2ull * n_quot, 0});
+        srcs.push_back(GlObserveSrc{D + open_trace.off + 2ull * c.num_columns, 2ull * c.num_columns, 0});
+        if (perm) srcs.push_back(GlObserveSrc{D + open_zs.off + 2ull * nz, 2ull * nz, 0});
+        TRY(fri_prove(c, L, D, H, T, oracles, srcs, batches, st, &pow_witness, ctx));
+    }
+    // everything the proof consists of, in one go
+    TRY(gl_memcpy_d2d(D + cap_trace.off, trace.cap_d.p, cap_words * 8, ctx));
+    if (perm) TRY(gl_memcpy_d2d(D + cap_zs.off, zs.cap_d.p, cap_words * 8, ctx));
+    TRY(gl_memcpy_d2d(D + cap_quot.off, quot.cap_d.p, cap_words * 8, ctx));
+    TRY(fetch(Span{fetch0.off, top - fetch0.off}));
+    TRY(gl_ctx_synchronize(ctx));
+    TRY(st.mark(9));
+    TRY(fri_check_pow(c, L, H, pow_witness));
+    // ---- the wire format of StarkProofWithPublicInputs (include/plonky2_hip.h) ----
+    Bytes out;
+    out.keccak = c.keccak();
+    out.hashes(H + cap_trace.off, cap_words / 4);
+    if (perm) out.hashes(H + cap_zs.off, cap_words / 4);
+    out.hashes(H + cap_quot.off, cap_words / 4);
+    out.fields(H + open_trace.off, 4ull * c.num_columns);  // local_values, next_values
+    if (perm) out.fields(H + open_zs.off, 4ull * nz);      // permutation_zs, permutation_zs_next
+    out.fields(H + open_quot.off, 2ull * n_quot);          // quotient_polys
+    fri_write(out, c, L, H, oracles, pow_witness);
+    out.fields(H + hostin.off, npi);
+    TRY(bytes_out(out, proof, proof_len));
+    return st.mark(10);
 }
 
 }  // extern "C"

@@ -1,0 +1,60 @@
+// stark.h — internal interface of the STARK kernels (stark.hip): starky's permutation Z polynomials and its constraint quotient,
+// the constraints given as ONE register program for the whole STARK (the GlGateInstr encoding with the STARK opcodes of
+// include/plonky2_hip.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "ntt.h"
+
+namespace plonky2_hip {
+
+constexpr uint32_t STARK_MAX_CHALLENGES = 4;  // num_challenges
+constexpr uint32_t STARK_MAX_QDF = 16;        // quotient_degree_factor = the permutation batch size = the number of challenge sets
+
+// What gl_stark_create checks once, on the host, before anything is allocated: opcodes of a STARK program only (no LOAD_CONST),
+// columns / public inputs / immediates / registers in range, a register written before it is read, the ACC contract (weights
+// below 2^32; between two ACCRs of an accumulator sum of weights * (2^32 - 1) < 2^63; no ACCR of an empty accumulator), and at
+// least one EMIT. Returns false and fills `error`.
+bool stark_program_validate(const uint16_t *instrs, uint32_t num_instrs, const uint64_t *imms, uint32_t num_imms, uint32_t num_columns,
+                            uint32_t num_public_inputs, std::string *error);
+
+// The permutation pairs of a STARK in device memory: pair p is column_pairs[pair_bounds[p] .. pair_bounds[p + 1]), a column pair
+// the two words (lhs, rhs).
+struct StarkPairsDev {
+    const uint32_t *column_pairs = nullptr;  // device, 2 per column pair
+    const uint32_t *pair_bounds = nullptr;   // device, num_pairs + 1
+    uint32_t num_pairs = 0;
+};
+
+// challenge set s, challenge c: (beta, gamma) = h_challenges[2 * (s * num_challenges + c) + {0, 1}] — the order they are drawn in
+// (get_n_permutation_challenge_sets, starky/src/permutation.rs:153-179); qdf sets.
+uint32_t stark_num_zs(uint32_t num_pairs, uint32_t num_challenges, uint32_t qdf);
+
+// out: [num_zs][n] value columns (compute_permutation_z_polys, permutation.rs:66-118)
+hipError_t stark_permutation_zs(const NttTables &tb, const uint64_t *trace, uint64_t trace_stride, const StarkPairsDev &pairs,
+                                const uint64_t *h_challenges, uint32_t num_challenges, uint32_t qdf, uint32_t log_n, uint64_t *out,
+                                hipStream_t stream);
+
+struct StarkQuotientArgs {
+    const uint16_t *instrs;  // device, 4 x u16 per instruction
+    uint32_t num_instrs;
+    const uint64_t *imms;           // device, may be null without immediates
+    const uint64_t *public_inputs;  // device, canonical; may be null without public inputs
+    const uint64_t *trace_lde, *zs_lde;  // column-major LDEs in bit-reversed row order; zs_lde null without pairs
+    uint64_t column_stride;              // >= n << rate_bits
+    StarkPairsDev pairs;
+    const uint64_t *alphas, *challenges;  // host
+    uint32_t num_challenges, qdf, degree_bits, rate_bits;
+};
+
+// out: [num_challenges][n << log2_ceil(qdf)] quotient VALUES on the coset 7 * <w>, natural order (compute_quotient_polys,
+// starky/src/prover.rs:199-319 up to the coset_ifft)
+hipError_t stark_quotient_values(const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream);
+
+// capi.hip: makes the device of `ctx` current and returns its tables and workspace
+hipError_t ctx_tables(void *ctx, const NttTables **out);
+
+}  // namespace plonky2_hip
