@@ -583,7 +583,10 @@ void gl_bytes_free(uint8_t *p);
  * Opcodes 11..14 exist in STARK programs only: gate programs refuse them as they refuse any unknown opcode. The consumer is starky's
  * (constraint_consumer.rs:53-76), not plonk's reduce_with_powers: for every challenge acc <- acc * alpha + constraint in emission
  * order. gl_stark_create validates the program once, on the host: no LOAD_CONST or unknown opcode, columns / public inputs /
- * immediates / registers in range, every register written before it is read, the ACC contract, at least one EMIT.
+ * immediates / registers in range, every register written before it is read, the ACC contract, at least one EMIT. The ACC contract
+ * as enforced: per accumulator, the sum of weight * (2^32 - 1) over the ACCs since its last ACCR stays below 2^63 (weights are the
+ * immediates reduced mod p, each below 2^32); the sum is kept in 128 bits, so that two weights near 2^32 are refused and do not
+ * wrap to a small bound. A single weight 2^31 is the largest sum that passes; the four accumulators are bounded separately.
  *
  * Permutation pairs (PermutationPair::column_pairs): pair p is the column pairs h_pair_bounds[p] .. h_pair_bounds[p + 1] of
  * h_column_pairs, two words (lhs, rhs) each. The instances cartesian_product(pairs, 0..num_challenges) are batched by
@@ -628,7 +631,10 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
 /* The two kernels of gl_stark_prove alone, with host challenges. h_challenges: the qdf challenge sets in the order they are drawn
  * (permutation.rs:153-179): (beta, gamma) of set s, challenge c at h_challenges[2 * (s * num_challenges + c)].
  * gl_stark_permutation_zs: d_trace value columns at pitch trace_stride >= n -> d_zs [num_z][n] value columns
- * (compute_permutation_z_polys). GL_E_INVALID for a STARK without pairs. */
+ * (compute_permutation_z_polys). GL_E_INVALID for a STARK without pairs. The trace need not satisfy anything. A ZERO DENOMINATOR —
+ * a row on which the product of a batch's right-hand sides gamma + sum_j beta^j row[rhs_j] vanishes — gives that row the quotient 0
+ * (0^(p-2) = 0; the reference's batch inversion panics instead): Z[r + 1 ..] of that batch are all 0, no error is reported, and the
+ * proof built on such Zs fails the permutation check at the verifier. */
 GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
                                 void *ctx);
 /* gl_stark_quotient_polys: compute_quotient_polys (prover.rs:199-319). d_trace_lde / d_zs_lde: the d_lde of gl_commit_from_values of

@@ -201,7 +201,7 @@ bool load_challenges(PermChallenges *ch, const uint64_t *h_challenges, uint32_t 
 bool stark_program_validate(const uint16_t *instrs, uint32_t num_instrs, const uint64_t *imms, uint32_t num_imms, uint32_t num_columns,
                             uint32_t num_public_inputs, std::string *error) {
     bool written[SP_MAX_REGS] = {};
-    uint64_t acc_bound[4] = {0, 0, 0, 0};
+    unsigned __int128 acc_bound[4] = {0, 0, 0, 0};  // 128 bits as in gate_jit.hip: two weights near 2^32 pass 2^64
     bool acc_used[4] = {false, false, false, false};
     uint32_t emitted = 0;
     auto bad = [&](uint32_t pc, const std::string &what) {
@@ -224,8 +224,8 @@ bool stark_program_validate(const uint16_t *instrs, uint32_t num_instrs, const u
         if (op == SP_ACC) {
             if (dst >= 4) return bad(pc, "ACC: accumulator out of range");
             if (b >= num_imms || imms[b] % glh::P >= (1ull << 32)) return bad(pc, "ACC: the immediate is missing / not below 2^32");
-            acc_bound[dst] += (imms[b] % glh::P) * 0xFFFFFFFFull;
-            if (acc_bound[dst] >= (1ull << 63)) return bad(pc, "ACC: the accumulator could reach 2^63 before its ACCR");
+            acc_bound[dst] += (unsigned __int128)(imms[b] % glh::P) * 0xFFFFFFFFull;
+            if (acc_bound[dst] >= ((unsigned __int128)1 << 63)) return bad(pc, "ACC: the accumulator could reach 2^63 before its ACCR");
             acc_used[dst] = true;
         } else if (op == SP_ACCR) {
             if (a >= 4) return bad(pc, "ACCR: accumulator out of range");

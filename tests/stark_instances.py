@@ -1,4 +1,4 @@
-"""Three STARKs as data (TEST INFRASTRUCTURE): shape, permutation pairs, the constraint program in the encoding of
+"""Three STARKs and one family of STARKs as data (TEST INFRASTRUCTURE): shape, permutation pairs, the constraint program in the encoding of
 include/plonky2_hip.h (assembled with plonky2_gpu_amd.stark.StarkAsm), the same constraints as a hand-written closure over a field
 object (tests/stark_ref.py Base / Ext), and a trace generator.
 
@@ -8,6 +8,11 @@ B  5 columns, degree 3 (qdf 2, qdb 1), 2 public inputs, a program that uses ever
    column pairs — so that num_pairs * num_challenges is odd for 1 and 3 challenges: several batches, the last one short.
 C  5 columns, degree 4 (qdf 3, qdb 2: the chunk copy and the tail check of a quotient_degree_factor that is no power of two),
    3 public inputs, no permutation pairs.
+D(d)  the family of constraint degree d = 2 .. 17 (qdf d - 1 up to the library's limit of 16): 4 columns, one public input,
+   c0' = c0 + 1, c1' = c1^(d-1) c0 + K, c0 starts at pi[0]; columns 2 and 3 hold the rows (c0, c1) under one permutation, pairs
+   [[(0, 2), (1, 3)], [(2, 0)]]: with at most 4 challenges never more than 8 instances, so one short batch from qdf 8 on.
+   D(d, public_input=False) starts c0 at an immediate instead: no public inputs at all. D(d, columns=5) has a fifth column
+   c4' = c4 + c0, for the Keccak hasher, which cannot hash leaves of 4 elements.
 
 Degrees: a constraint of degree d in the columns leaves a quotient of degree < (d - 1) n as a transition (times z_last) or on all
 rows; behind a Lagrange selector it may have degree d - 1 at most."""
@@ -151,4 +156,60 @@ def _c_trace(degree_bits, seed=0):
 
 C = TestStark("C", 5, 3, 4, [], _c_program(), _c_closure, _c_trace)
 
+
+
+# ---------------------------------------------------------------- D(d): degree d, qdf = d - 1
+D_K = 0xFEDCBA9876543  # an immediate above 2^32
+D_START = 77  # where c0 starts without a public input
+
+
+def D(d, public_input=True, columns=4):
+    assert 2 <= d <= 17 and columns in (4, 5)
+
+    def program():
+        a = StarkAsm()
+        c0, c1 = a.local(0), a.local(1)
+        a.emit_first_row(a.sub(c0, a.pi(0) if public_input else a.imm(D_START)))
+        a.emit_transition(a.sub(a.next(0), a.add(c0, a.imm(1))))  # c0' = c0 + 1
+        power = c1
+        for _ in range(d - 2):
+            power = a.mul(power, c1)
+        a.emit_transition(a.sub(a.sub(a.next(1), a.mul(power, c0)), a.imm(D_K)))  # c1' = c1^(d-1) c0 + K: degree d
+        if columns == 5:
+            a.emit_transition(a.sub(a.sub(a.next(4), a.local(4)), c0))  # c4' = c4 + c0
+        return a
+
+    def closure(F, local, nxt, pis, c):
+        c.constraint_first_row(F.sub(local[0], pis[0] if public_input else F.lift(D_START)))
+        c.constraint_transition(F.sub(nxt[0], F.add(local[0], F.one)))
+        power = local[1]
+        for _ in range(d - 2):
+            power = F.mul(power, local[1])
+        c.constraint_transition(F.sub(F.sub(nxt[1], F.mul(power, local[0])), F.lift(D_K)))
+        if columns == 5:
+            c.constraint_transition(F.sub(F.sub(nxt[4], local[4]), local[0]))
+
+    def make_trace(degree_bits, seed=0):
+        n = 1 << degree_bits
+        start = 500 + seed if public_input else D_START
+        c0 = [(start + r) % P for r in range(n)]
+        c1 = [(seed * 31 + 3) % P]
+        for r in range(n - 1):
+            c1.append((pow(c1[r], d - 1, P) * c0[r] + D_K) % P)
+        sigma = np.random.default_rng(seed + 17).permutation(n)
+        cols = [c0, c1, [c0[s] for s in sigma], [c1[s] for s in sigma]]  # the rows (c0, c1) permuted together
+        if columns == 5:
+            c4 = [(seed + 9) % P]
+            for r in range(n - 1):
+                c4.append((c4[r] + c0[r]) % P)
+            cols.append(c4)
+        return cols, [c0[0]] if public_input else []
+
+    name = "D%d%s%s" % (d, "" if public_input else "n", "" if columns == 4 else "k")
+    return TestStark(name, columns, int(public_input), d, [[(0, 2), (1, 3)], [(2, 0)]], program(), closure, make_trace)
+
+
+# D at the degrees the tests use: qdf 4 (one full batch at 2 challenges), 5 (no power of two: chunk copy, batches 5 + 1), 8, 16 (the
+# limit); "n": no public inputs; "k": five columns
 STARKS = {"A": A, "B": B, "C": C}
+STARKS.update({s.name: s for s in (D(5), D(6), D(9), D(17), D(5, public_input=False), D(5, columns=5), D(17, columns=5))})

@@ -645,3 +645,188 @@ def test_blinded_proof_from_lifted_inputs(gpu):
     nc = pg.NativeCircuit(gpu, lifted, compile_gates=True)
     assert nc.prove_bytes(l_w, l_p, salts=salts) == want
     nc.close()
+
+
+# ---- STARKs: gl_stark_permutation_zs, gl_stark_quotient_polys, gl_stark_prove ---------------------------------------------------
+
+def _stark_modules():
+    import generic_prove_ref as gr
+    import stark_fuzz as sf
+    import stark_instances as si
+    import stark_ref as sr
+
+    return gr, sf, si, sr
+
+
+def _small_sets(rng, qdf, num_challenges):
+    """[set][challenge] (beta, gamma): liftable values, 2^32 - 2 and 2^32 - 3 (lifted: 2^64 - 1, 2^64 - 2) among them"""
+    sets = [[(int(rng.integers(0, LIFTABLE)), int(rng.integers(0, LIFTABLE))) for _ in range(num_challenges)] for _ in range(qdf)]
+    sets[0][0] = (TOP, TOP2)
+    sets[-1][-1] = (sets[-1][-1][0], TOP)
+    return sets, [[(lift_scalar(b), lift_scalar(g)) for b, g in s] for s in sets]
+
+
+def _native_stark(gpu, stark, degree_bits, num_challenges, rate_bits, immediates=None, **fri):
+    import plonky2_gpu_amd as pg
+
+    _, _, si, _ = _stark_modules()
+    desc = stark.desc(degree_bits, num_challenges, si.fri_params(rate_bits=rate_bits, **fri))
+    if immediates is not None:
+        desc.immediates = list(immediates)  # as they are: StarkDesc reduces its own
+    return pg.NativeStark(gpu, desc)
+
+
+@pytest.mark.parametrize("name,degree_bits,num_challenges", [("B", 11, 3), ("D17", 3, 4)])
+def test_stark_permutation_zs(gpu, name, degree_bits, num_challenges):
+    """the trace (any words: the Zs of a trace that satisfies nothing are as well defined), betas and gammas. B at 2^11 rows:
+    5 Zs over two blocks of the prefix product each; D(17): 8 instances in one batch, 16 challenge sets"""
+    _, _, si, sr = _stark_modules()
+    stark = si.STARKS[name]
+    rng = np.random.default_rng(1500 + degree_bits)
+    n = 1 << degree_bits
+    trace = field_data(rng, (stark.num_columns, n))
+    l_trace, count = lift(trace, rng, 0.6)
+    assert count > trace.size // 4
+    sets, l_sets = _small_sets(rng, sr.quotient_degree_factor(stark), num_challenges)
+    assert l_sets[0][0] == (M64, M64 - 1)
+    ns = _native_stark(gpu, stark, degree_bits, num_challenges, 4)
+    try:
+        canon_out = ns.permutation_zs(trace, sets)
+        _check(ns.permutation_zs(l_trace, l_sets), canon_out)
+        _check(ns.permutation_zs(l_trace, l_sets, trace_stride=n + 6), canon_out)
+    finally:
+        ns.close()
+    exp = sr.compute_permutation_z_polys(stark, num_challenges, trace.tolist(), sets)
+    assert (canon_out == np.array(exp, dtype=np.uint64)).all()
+
+
+def _stark_quotient_data(rng, stark, degree_bits, rate_bits, num_challenges, sr):
+    n_ext = 1 << (degree_bits + rate_bits)
+    trace = field_data(rng, (stark.num_columns, n_ext))
+    zs = field_data(rng, (sr.num_zs(stark, num_challenges), n_ext))
+    l_trace, c1 = lift(trace, rng, 0.6)
+    l_zs, c2 = lift(zs, rng, 0.6)
+    assert c1 + c2 > (trace.size + zs.size) // 4
+    sets, l_sets = _small_sets(rng, sr.quotient_degree_factor(stark), num_challenges)
+    alphas = [TOP, TOP2, int(rng.integers(0, LIFTABLE)), 7][:num_challenges]
+    pis = [TOP2, int(rng.integers(0, LIFTABLE)), TOP][: stark.num_public_inputs]
+    canon = (trace, zs, sets, alphas, pis)
+    lifted = (l_trace, l_zs, l_sets, [lift_scalar(a) for a in alphas], [lift_scalar(x) for x in pis])
+    assert all(x >= P for x in lifted[3] + lifted[4])
+    return canon, lifted
+
+
+def _run_quotient(gpu, ns, data, stride=None):
+    trace, zs, sets, alphas, pis = data
+    d_t = _buf(gpu, trace)
+    d_z = _buf(gpu, zs) if zs is not None else None
+    return ns.quotient_polys(d_t, d_z, stride or trace.shape[1], alphas, sets, pis)
+
+
+@pytest.mark.parametrize("name,degree_bits,rate_bits,num_challenges", [("B", 3, 2, 3), ("D17", 2, 4, 4)])
+def test_stark_quotient_polys(gpu, name, degree_bits, rate_bits, num_challenges):
+    """the trace and Z "LDEs" (any words), alphas, betas, gammas and public inputs lifted; then, through a second handle, the
+    immediates of the description lifted as well — ACC weights among B's: gl_stark_create reduces them before it checks the
+    ACC contract. SP_ACC adds the 32-bit halves of the raw register: a lifted word x + p has other halves than x"""
+    _, sf, si, sr = _stark_modules()
+    stark = si.STARKS[name]
+    rng = np.random.default_rng(1600 + degree_bits)
+    canon, lifted = _stark_quotient_data(rng, stark, degree_bits, rate_bits, num_challenges, sr)
+    l_imms = [lift_scalar(v) for v in stark.immediates]
+    assert sum(a != b for a, b in zip(l_imms, stark.immediates)) > len(l_imms) // 4
+    ns = _native_stark(gpu, stark, degree_bits, num_challenges, rate_bits)
+    ns2 = _native_stark(gpu, stark, degree_bits, num_challenges, rate_bits, immediates=l_imms)
+    try:
+        canon_out = _run_quotient(gpu, ns, canon)
+        _check(_run_quotient(gpu, ns, lifted), canon_out)
+        _check(_run_quotient(gpu, ns2, canon), canon_out)
+        _check(_run_quotient(gpu, ns2, lifted), canon_out)
+    finally:
+        ns.close()
+        ns2.close()
+    case = dict(stark=stark, degree_bits=degree_bits, rate_bits=rate_bits, num_challenges=num_challenges)
+    assert (canon_out == sf.reference_quotient(case, *canon)).all()
+
+
+def test_stark_quotient_polys_extreme_accumulators(gpu):
+    """every "LDE" word 2^64 - 1 or p - 1 (the data of test_reduce_polys_base's extreme case) under ACC weights 2^31 on one
+    accumulator and 2^30 - 1 twice on another: the largest accumulator halves the contract permits with the largest register
+    halves a u64 can have. The reference receives the canonical words 2^32 - 2 and p - 1."""
+    _, sf, si, sr = _stark_modules()
+    from plonky2_gpu_amd.stark import StarkAsm
+
+    a = StarkAsm()
+    x, y = a.local(0), a.next(1)
+    a.acc(x, 1 << 31, q=2)
+    a.acc(x, (1 << 30) - 1, q=1)
+    a.acc(y, (1 << 30) - 1, q=1)
+    a.emit(a.accr(2))
+    a.emit_transition(a.accr(1))
+    a.emit_first_row(a.mul(x, y))
+    a.emit_last_row(a.sub(x, y))
+    a.emit(a.add(x, y))
+    instrs, imms = a.program()
+    sr.validate_program(instrs, imms, 2, 0)
+    stark = sf.FuzzStark(2, 0, 3, [], instrs, imms)
+    degree_bits, rate_bits, nch = 4, 2, 2
+    case = dict(stark=stark, degree_bits=degree_bits, rate_bits=rate_bits, num_challenges=nch)
+    rng = np.random.default_rng(1700)
+    pick = rng.random((2, 1 << (degree_bits + rate_bits))) < 0.5
+    trace = np.where(pick, np.uint64(TOP), np.uint64(P - 1)).astype(np.uint64)
+    l_trace = np.where(pick, np.uint64(M64), np.uint64(P - 1)).astype(np.uint64)
+    assert int(pick.sum()) > pick.size // 4
+    alphas = [TOP, TOP2]
+    import plonky2_gpu_amd as pg
+
+    ns = pg.NativeStark(gpu, pg.stark.StarkDesc(degree_bits, 2, 0, 3, nch, si.fri_params(rate_bits=rate_bits), instrs, imms, []))
+    try:
+        canon_out = _run_quotient(gpu, ns, (trace, None, None, alphas, []))
+        _check(_run_quotient(gpu, ns, (l_trace, None, None, [M64, M64 - 1], [])), canon_out)
+    finally:
+        ns.close()
+    exp = sf.reference_quotient(case, trace, None, None, alphas, [])
+    assert exp.any() and (canon_out == exp).all()
+
+
+def _proof_words(x):
+    """every integer of a parsed proof (hashes of the Keccak hasher are bytes: no field words)"""
+    if isinstance(x, dict):
+        return [w for v in x.values() for w in _proof_words(v)]
+    if isinstance(x, (list, tuple)):
+        return [w for v in x for w in _proof_words(v)]
+    if isinstance(x, (int, np.integer)):
+        return [int(x)]
+    return []
+
+
+def test_stark_proof_from_a_lifted_trace(gpu):
+    """gl_stark_prove on a valid trace of B (two of its five columns are counters: small values) with nearly every liftable cell
+    and both public inputs lifted: the bytes of the canonical trace's proof, which are the reference's; every field word of the
+    proof is canonical, the public inputs at its end included"""
+    from oracle import accel
+    from plonky2_gpu_amd import stark as pstark
+
+    gr, _, si, sr = _stark_modules()
+    degree_bits, nch = 6, 2
+    fri = dict(cap_height=1, arity_bits=(2, 1))
+    trace, pis = si.B.make_trace(degree_bits, seed=3)
+    trace = np.array(trace, dtype=np.uint64)
+    rng = np.random.default_rng(1800)
+    l_trace, count = lift(trace, rng, 0.95)
+    l_pis = [lift_scalar(x) for x in pis]
+    assert count > trace.size // 4 and all(x >= P for x in l_pis)
+    ns = _native_stark(gpu, si.B, degree_bits, nch, 2, **fri)
+    try:
+        want = ns.prove_bytes(trace, pis)
+        got = ns.prove_bytes(l_trace, l_pis)
+    finally:
+        ns.close()
+    assert got == want
+    parsed = pstark.proof_from_bytes(got, ns.desc)
+    words = _proof_words(parsed)
+    assert len(words) > 500 and all(0 <= w < P for w in words)
+    assert [int(x) for x in parsed["public_inputs"]] == [int(x) for x in pis]
+    assert got[-16:] == np.array(pis, dtype="<u8").tobytes()
+    with accel.c_backend():
+        hasher = gr.PoseidonHasher()
+        assert want == sr.proof_bytes(hasher, sr.prove(hasher, si.B, nch, si.fri_params(rate_bits=2, **fri), trace.tolist(), pis))

@@ -1,6 +1,7 @@
 """STARK proofs on the device (gl_stark_create / gl_stark_prove and the two kernels alone) against tests/stark_ref.py, bit for bit:
 there is no tolerance anywhere. The STARKs A (Fibonacci, qdf 1), B (degree 3, every opcode, three permutation pairs, qdf 2) and C
-(degree 4, qdf 3, no pairs) are tests/stark_instances.py's. The reference runs with oracle.accel.c_backend (its Poseidon, trees and
+(degree 4, qdf 3, no pairs) and the family D(d) (degree d up to 17: qdf up to the library's 16, with up to 4 challenges; a variant without
+public inputs, a variant with five columns for Keccak) are tests/stark_instances.py's. The reference runs with oracle.accel.c_backend (its Poseidon, trees and
 transforms in C): the algebra of the STARK stays Python."""
 import ctypes
 import functools
@@ -78,6 +79,70 @@ def test_permutation_zs_at_two_scan_blocks(gpu):
         ns.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,degree_bits,num_challenges", [("A", 10, 2), ("B", 13, 3), ("D17", 3, 4)])
+def test_permutation_zs_at_one_and_at_eight_scan_blocks_and_at_the_limits(gpu, name, degree_bits, num_challenges):
+    """2^10 rows: exactly one block of the prefix product; 2^13 rows of B with 3 challenges: 5 Zs over 8 blocks each (the block
+    totals of Z b start at b * 8), at the tight and at a padded trace pitch; D(17) with 4 challenges: 8 instances in one short batch
+    of 16, the challenge sets 0 .. 7 of 16"""
+    stark = si.STARKS[name]
+    trace, _ = _trace(name, degree_bits)
+    sets = _challenge_sets(300 + degree_bits, sr.quotient_degree_factor(stark), num_challenges)
+    exp = np.array(sr.compute_permutation_z_polys(stark, num_challenges, trace, sets), dtype=np.uint64)
+    assert exp.shape == (sr.num_zs(stark, num_challenges), 1 << degree_bits) and (exp[:, 0] == 1).all() and exp.all()
+    ns = _native(gpu, stark, degree_bits, num_challenges, si.fri_params(rate_bits=4))
+    try:
+        n = 1 << degree_bits
+        for stride in (n, n + 6):
+            got = ns.permutation_zs(trace, sets, trace_stride=stride)
+            bad = np.argwhere(got != exp)
+            assert bad.size == 0, ("trace pitch", stride, "first (Z, row) that differs", bad[0].tolist(), len(bad))
+    finally:
+        ns.close()
+
+
+@pytest.mark.gpu
+def test_permutation_zs_at_more_block_totals_than_one_workgroup_has_threads(gpu):
+    """2^19 rows are 512 blocks of the prefix product: every thread of the workgroup that scans the block totals takes two. The
+    expected values come from stark_fuzz.fast_permutation_z_polys (one batch inversion instead of one inversion per row), which
+    tests/test_stark_fuzz.py holds against sr.compute_permutation_z_polys"""
+    import stark_fuzz as sf
+
+    stark, degree_bits = si.A, 19
+    trace, _ = _trace("A", degree_bits)
+    sets = _challenge_sets(19, 1, 1)
+    exp = np.array(sf.fast_permutation_z_polys(stark, 1, trace, sets), dtype=np.uint64)
+    assert exp.shape == (1, 1 << degree_bits) and exp.all()
+    ns = _native(gpu, stark, degree_bits, 1, si.fri_params(rate_bits=1))
+    try:
+        got = ns.permutation_zs(trace, sets)
+        bad = np.argwhere(got != exp)
+        assert bad.size == 0, ("first (Z, row) that differs", bad[0].tolist(), len(bad))
+    finally:
+        ns.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("degree_bits,row", [(3, 2), (11, 1500)])
+def test_a_zero_denominator_gives_quotient_zero(gpu, degree_bits, row):
+    """the rule of include/plonky2_hip.h (gl_stark_permutation_zs): where the product of the right-hand sides vanishes the row's
+    quotient is 0, as the reference's pow(0, p - 2) is, and every later Z value is 0. A has one pair of single columns (2, 3): the
+    right-hand cell of `row` becomes p - gamma"""
+    trace, _ = _trace("A", degree_bits)
+    trace = [list(col) for col in trace]
+    sets = _challenge_sets(55 + degree_bits, 1, 1)
+    trace[3][row] = (P - sets[0][0][1]) % P
+    exp = np.array(sr.compute_permutation_z_polys(si.A, 1, trace, sets), dtype=np.uint64)
+    assert exp[0, : row + 1].all() and not exp[0, row + 1 :].any()
+    ns = _native(gpu, si.A, degree_bits, 1, si.fri_params(rate_bits=1))
+    try:
+        got = ns.permutation_zs(trace, sets)
+        assert not got[0, row + 1 :].any()
+        assert (got == exp).all()
+    finally:
+        ns.close()
+
+
 # ---------------------------------------------------------------- the quotient
 @functools.lru_cache(maxsize=None)
 def _quotient_case(name, degree_bits, rate_bits):
@@ -86,7 +151,7 @@ def _quotient_case(name, degree_bits, rate_bits):
     from oracle import accel
 
     stark = si.STARKS[name]
-    num_challenges = 3 if name == "B" else 2
+    num_challenges = {"B": 3, "D6": 3, "D17": 4}.get(name, 2)
     trace, pis = _trace(name, degree_bits)
     rng = np.random.default_rng(1000 * degree_bits + rate_bits)
     alphas = [int(x) for x in rng.integers(0, P, size=num_challenges, dtype=np.uint64)]
@@ -107,6 +172,18 @@ def _quotient_case(name, degree_bits, rate_bits):
 def test_quotient_polys_equal_the_reference(gpu, name, rate_bits, degree_bits):
     """step > 1 (rate_bits above qdb) and step = 1, the wrap of the next row at the end of the domain, the LDEs at the tight and at a
     padded column pitch (guards and pads checked: the kernel only reads them)"""
+    _check_quotient(gpu, name, rate_bits, degree_bits)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,degree_bits,rate_bits", [("D5n", 3, 2), ("D5n", 3, 3), ("D6", 3, 3), ("D17", 3, 4), ("D17", 1, 5), ("A", 1, 1), ("A", 2, 2)])
+def test_quotient_polys_at_the_limits_equal_the_reference(gpu, name, degree_bits, rate_bits):
+    """D5n: no public inputs at all (an empty public-inputs buffer); D6: qdf 5 in a domain of 8 n points with 3 challenges; D17: qdf 16
+    with 4 challenges, all 16 values of Z_H on the coset, 8 instances in one short batch, also on two rows; A on two and four rows"""
+    _check_quotient(gpu, name, rate_bits, degree_bits)
+
+
+def _check_quotient(gpu, name, rate_bits, degree_bits):
     stark = si.STARKS[name]
     trace_lde, zs_lde, sets, alphas, pis, exp = _quotient_case(name, degree_bits, rate_bits)
     qdf = sr.quotient_degree_factor(stark)
@@ -156,6 +233,16 @@ PROOFS = [
     ("C", 3, 1, 2, 2, (), "keccak"),
     ("C", 9, 2, 2, 0, (3,), "keccak"),
     ("B", 10, 2, 1, 2, (1, 2), "poseidon"),
+    ("D5", 3, 2, 2, 0, (1, 2), "poseidon"),  # qdf 4: one full batch of 4 instances
+    ("D6", 3, 3, 3, 1, (3,), "poseidon"),  # qdf 5, qdb 3: the chunk copy of 5 out of 8, batches of 5 + 1, the tail check
+    ("D9", 4, 1, 3, 2, (2,), "poseidon"),  # qdf 8
+    ("D17", 3, 4, 4, 0, (1, 2), "poseidon"),  # the limits: qdf 16, 4 challenges, 64 quotient polynomials, 8 instances in one short batch
+    ("A", 1, 2, 1, 0, (), "poseidon"),  # the smallest traces
+    ("A", 2, 1, 2, 1, (1,), "poseidon"),
+    ("D17", 1, 4, 4, 0, (1,), "poseidon"),  # the smallest trace at the largest qdf
+    ("D5n", 3, 2, 2, 0, (1, 2), "poseidon"),  # no public inputs
+    ("D5k", 3, 2, 2, 0, (3,), "keccak"),  # five columns: Keccak cannot hash a leaf of four
+    ("D17k", 1, 3, 4, 1, (), "keccak"),
 ]
 
 
@@ -282,6 +369,23 @@ def test_a_corrupted_trace_of_c_fails_the_trim(gpu):
         assert e.value.code == pg.GL_E_INVALID and "Quotient has failed" in str(e.value)
         good, pis = _trace("C", 4)
         assert ns.prove_bytes(good, pis) == _reference_proof("C", 4, 2, 2, 0, (2,), "poseidon")  # the handle is still usable
+    finally:
+        ns.close()
+
+
+@pytest.mark.gpu
+def test_a_corrupted_trace_of_d6_fails_the_trim(gpu):
+    """qdf 5 in a domain of 8 n: coefficients 5n .. 8n must vanish; after the refusal the handle proves a valid trace"""
+    import plonky2_gpu_amd as pg
+
+    trace, pis = _corrupted("D6", 3)
+    ns = _native(gpu, si.STARKS["D6"], 3, 3, si.fri_params(rate_bits=3, cap_height=1, arity_bits=(3,)))
+    try:
+        with pytest.raises(pg.Plonky2HipError) as e:
+            ns.prove_bytes(trace, pis)
+        assert e.value.code == pg.GL_E_INVALID and "Quotient has failed" in str(e.value)
+        good, pis = _trace("D6", 3)
+        assert ns.prove_bytes(good, pis) == _reference_proof("D6", 3, 3, 3, 1, (3,), "poseidon")
     finally:
         ns.close()
 

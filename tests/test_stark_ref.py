@@ -105,7 +105,7 @@ def test_this_starky_does_not_bind_unused_public_inputs():
     assert data[-8 * stark.num_public_inputs :] == np.array(proof["public_inputs"], dtype="<u8").tobytes()
 
 
-@pytest.mark.parametrize("name", ["A", "B", "C"])
+@pytest.mark.parametrize("name", sorted(si.STARKS))
 def test_interpreter_and_closures_agree_on_random_rows(name):
     """over the base field and over the extension, constraint by constraint and in the accumulators; random rows satisfy nothing,
     so every constraint is non-zero and a swapped operand or a wrong emit kind shows"""
@@ -121,7 +121,7 @@ def test_interpreter_and_closures_agree_on_random_rows(name):
             a, b = sr.Consumer(F, alphas, z_last, l_first, l_last), sr.Consumer(F, alphas, z_last, l_first, l_last)
             sr.eval_constraints(F, stark, local, nxt, pis, a, "program")
             sr.eval_constraints(F, stark, local, nxt, pis, b, "closure")
-            assert a.emitted == b.emitted and a.accs == b.accs and len(a.emitted) >= 5
+            assert a.emitted == b.emitted and a.accs == b.accs and len(a.emitted) >= (3 if name.startswith("D") else 5)  # D: 3 or 4
             assert all(c != F.zero for c in a.emitted)
 
 
