@@ -357,7 +357,8 @@ GlError gl_sponge_absorb(uint64_t *h_state, const uint64_t *h_inputs, uint32_t n
  * instead of challenges, d_out[0..4) = hash_n_to_hash_no_pad of everything observed since the reset (hash/hashing.rs:81-108; use it
  * with GL_CHALLENGER_RESET on a scratch challenger). Values a host holds (circuit digest, public inputs) are observed from a device
  * copy. The host fetches the challenges it needs itself with one gl_memcpy_d2h per step; kernels that can read a challenge from
- * device memory need no fetch at all (gl_fri_fold_device, gl_merkle_open_batch_device, gl_fri_proof_of_work_device). */
+ * device memory need no fetch at all (gl_fri_fold_device, gl_merkle_open_batch_device, gl_fri_proof_of_work_device). d_out, when
+ * given, must not overlap the 32 words of d_challenger (GL_E_INVALID): the step writes its outputs before it stores the transcript. */
 typedef struct GlObserveSrc {
     const uint64_t *d_ptr;
     uint64_t count;      /* field elements observed from this source */
@@ -372,6 +373,9 @@ typedef struct GlObserveSrc {
 #define GL_OBSERVE_KECCAK_DIGESTS UINT64_MAX
 #define GL_CHALLENGER_RESET 1u
 #define GL_CHALLENGER_HASH 2u
+/* Challenger::compact() (challenger.rs:149-155) before observing, as GL_CHALLENGER_RESET acts before observing: a non-empty input
+ * buffer is duplexed, then the output buffer is cleared. */
+#define GL_CHALLENGER_COMPACT 4u
 GlError gl_challenger_step(uint64_t *d_challenger, const GlObserveSrc *h_srcs, uint32_t n_srcs, uint32_t n_challenges, uint64_t *d_out,
                            uint32_t flags, void *ctx);
 
@@ -644,6 +648,77 @@ GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint
 GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
                                 const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
                                 uint64_t *d_quotient_polys, void *ctx);
+
+/* ---- Multi-table STARKs with cross-table lookups ---------------------------------------------------
+ * gl_stark_tables_create describes num_tables STARKs (each a GlStarkDesc with its own degree_bits, columns, program, permutation
+ * pairs and fri.reduction_arity_bits) tied together by cross-table lookups (CTLs); gl_stark_tables_prove is prove_with_traces
+ * (evm/src/prover.rs:66-421) over cross_table_lookup_data / eval_cross_table_lookup_checks (evm/src/cross_table_lookup.rs) and the
+ * three-batch FRI instance of evm/src/stark.rs:83-142. Nothing EVM-specific: the tables and the lookups are what the caller describes.
+ *
+ * A CTL COLUMN is constant + sum_j coeff_j * row[col_j] (Column::eval): CTL column k is the terms h_column_bounds[k] ..
+ * h_column_bounds[k + 1] of (h_term_columns, h_term_coeffs) plus h_column_constants[k]; no terms = a constant column. Coefficients
+ * and constants are any u64, reduced mod p. A TABLE-WITH-COLUMNS (TWC) t names table h_twc_table[t], the CTL columns
+ * h_twc_column_bounds[t] .. h_twc_column_bounds[t + 1] and the filter h_twc_filter[t]: the index of a CTL column, or
+ * GL_CTL_NO_FILTER. Term columns are columns of the TWC's table. LOOKUP l is the TWCs h_lookup_bounds[l] .. h_lookup_bounds[l + 1]:
+ * the LAST one is the looked table, the others are looking. (A verifier's `default` row is not part of the description.)
+ *
+ * THE CTL Zs of a table, in order: for every lookup, for every challenge c in 0..num_challenges, the looking TWCs in order and then
+ * the looked TWC each append one Z to the table they name. Z[i] = prod_{r <= i} s_r, s_r = gamma_c + sum_j beta_c^j column_j(row r)
+ * where the filter evaluates to 1 (as a field element: a word p + 1 is 1) and s_r = 1 where it evaluates to 0 — the INCLUSIVE
+ * prefix product (partial_products, :314-341). Any other filter value is GL_E_INVALID "Non-binary filter?". The Zs oracle of a
+ * table holds its permutation Zs, then its CTL Zs; the quotient's constraints are the program's, then the permutation checks, then
+ * per CTL Z, with select(f, x) = f x + 1 - f (f = 1 without a filter),
+ *   constraint_first_row(z - select(filter(local), combine(local))), constraint_transition(z' - z select(filter(next), combine(next))).
+ *
+ * TRANSCRIPT: every trace is committed; a fresh Challenger observes all trace caps in table order and yields num_challenges (beta,
+ * gamma) CTL challenges shared by all tables; then per table in order: compact(), the permutation challenge sets (with pairs), the
+ * Zs cap, alphas, the quotient cap, zeta, the openings (zeta batch, zeta g batch, then ctl_zs_last lifted to (x, 0)), prove_openings.
+ * The one Challenger runs on from table to table.
+ *
+ * gl_stark_tables_create refuses, with GL_E_INVALID and a message, before anything is allocated: whatever gl_stark_create refuses
+ * for a table; tables that differ in num_challenges, rate_bits, cap_height, proof_of_work_bits, num_query_rounds or hiding
+ * (reduction_arity_bits may differ); a table with public inputs; a table no lookup names ("No CTL?"); indices out of range; a
+ * lookup without a looking TWC, with unequal column counts or with filters on some of its TWCs only; constraint_degree < 3 for a
+ * table with a filtered CTL Z, < 2 with an unfiltered one; with GL_HASHER_KECCAK25 a Zs oracle of exactly 4 polynomials. */
+#define GL_CTL_NO_FILTER 4294967295u
+typedef struct GlStarkTablesDesc {
+    uint32_t struct_size; /* = sizeof(GlStarkTablesDesc) */
+    uint32_t num_tables;
+    const GlStarkDesc *tables;
+    const uint32_t *h_term_columns;
+    const uint64_t *h_term_coeffs;
+    const uint32_t *h_column_bounds; /* num_ctl_columns + 1, starting at 0, non-decreasing */
+    const uint64_t *h_column_constants;
+    uint32_t num_ctl_columns;
+    const uint32_t *h_twc_table, *h_twc_column_bounds /* num_twcs + 1 */, *h_twc_filter;
+    uint32_t num_twcs;
+    const uint32_t *h_lookup_bounds; /* num_lookups + 1 */
+    uint32_t num_lookups;
+} GlStarkTablesDesc;
+GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *desc, void **tables, void *ctx);
+void gl_stark_tables_destroy(void *tables);
+GlError gl_stark_tables_trim(void *tables);
+/* d_traces[k]: the trace of table k, [num_columns][2^degree_bits] value columns, left untouched. h_stage_ms: NULL or
+ * [num_tables][GL_STARK_STAGES], the stages of gl_stark_prove per table; stage 1 of a table is its permutation Zs plus its CTL Zs.
+ * All trace commitments stay alive until their table is proved: HBM use is the sum of the tables' trace LDEs plus one table's
+ * working set. WIRE FORMAT: the tables' StarkProofs (evm/src/proof.rs:103-257) in table order, each
+ *   trace_cap, permutation_ctl_zs_cap (always present), quotient_polys_cap;
+ *   the openings: local_values, next_values, permutation_ctl_zs, permutation_ctl_zs_next as extension elements; ctl_zs_last (the
+ *     CTL Zs only, at 1 / g), ONE field element each; quotient_polys as extension elements;
+ *   the FRI proof as write_fri_proof writes it.
+ * There are no public inputs. The non-binary filter is reported at the proof's next host synchronisation. */
+GlError gl_stark_tables_prove(const void *tables, const uint64_t *const *d_traces, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms,
+                              void *ctx);
+/* The two kernels alone, synchronous, with host challenges. h_ctl_challenges: (beta, gamma) of challenge c at [2 c].
+ * gl_stark_tables_ctl_zs: d_trace value columns of table `table` at pitch trace_stride >= n -> d_zs [num CTL Zs of the table][n]
+ * value columns; GL_E_INVALID "Non-binary filter?" as above. gl_stark_tables_quotient_polys: gl_stark_quotient_polys of that table
+ * with the CTL checks; d_zs_lde holds the permutation Zs, then the CTL Zs; h_perm_challenges NULL without pairs. A filter's LDE
+ * is not binary off the subgroup: the quotient evaluates select() as written and reports nothing. */
+GlError gl_stark_tables_ctl_zs(const void *tables, uint32_t table, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_ctl_challenges,
+                               uint64_t *d_zs, void *ctx);
+GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde,
+                                       uint64_t column_stride, const uint64_t *h_alphas, const uint64_t *h_perm_challenges,
+                                       const uint64_t *h_ctl_challenges, uint64_t *d_quotient_polys, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.

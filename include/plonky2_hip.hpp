@@ -344,4 +344,34 @@ class Stark {
     uint32_t num_public_inputs_;
 };
 
+// Several STARKs tied by cross-table lookups (plonky2_hip.h "Multi-table STARKs with cross-table lookups"): gl_stark_tables_create
+// on construction, gl_stark_tables_destroy on destruction. prove() = gl_stark_tables_prove: the tables' StarkProofs in table order.
+class StarkTables {
+  public:
+    StarkTables(const Context &ctx, const GlStarkTablesDesc &desc, Hasher hasher = Hasher::Poseidon) : num_tables_(desc.num_tables) {
+        check(gl_stark_tables_create((uint32_t)hasher, &desc, &ptr_, ctx.get()));
+    }
+    ~StarkTables() {
+        if (ptr_) gl_stark_tables_destroy(ptr_);
+    }
+    StarkTables(const StarkTables &) = delete;
+    StarkTables &operator=(const StarkTables &) = delete;
+    void *get() const { return ptr_; }
+    // d_traces[k]: [num_columns][2^degree_bits] value columns of table k in HBM
+    std::vector<uint8_t> prove(const Context &ctx, const std::vector<const uint64_t *> &d_traces) const {
+        if (d_traces.size() != num_tables_) throw std::invalid_argument("StarkTables::prove: one trace per table");
+        uint8_t *bytes = nullptr;
+        uint64_t len = 0;
+        check(gl_stark_tables_prove(ptr_, d_traces.data(), &bytes, &len, nullptr, ctx.get()));
+        std::vector<uint8_t> out(bytes, bytes + len);
+        gl_bytes_free(bytes);
+        return out;
+    }
+    void trim() const { check(gl_stark_tables_trim(ptr_)); }
+
+  private:
+    void *ptr_ = nullptr;
+    uint32_t num_tables_;
+};
+
 }  // namespace plonky2_hip

@@ -135,6 +135,27 @@ class GlStarkDesc(ctypes.Structure):
     ]
 
 
+class GlStarkTablesDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("num_tables", ctypes.c_uint32),
+        ("tables", ctypes.POINTER(GlStarkDesc)),
+        ("h_term_columns", ctypes.c_void_p),
+        ("h_term_coeffs", ctypes.c_void_p),
+        ("h_column_bounds", ctypes.c_void_p),
+        ("h_column_constants", ctypes.c_void_p),
+        ("num_ctl_columns", ctypes.c_uint32),
+        ("h_twc_table", ctypes.c_void_p),
+        ("h_twc_column_bounds", ctypes.c_void_p),
+        ("h_twc_filter", ctypes.c_void_p),
+        ("num_twcs", ctypes.c_uint32),
+        ("h_lookup_bounds", ctypes.c_void_p),
+        ("num_lookups", ctypes.c_uint32),
+    ]
+
+
+GL_CTL_NO_FILTER = 0xFFFFFFFF
+GL_CHALLENGER_RESET, GL_CHALLENGER_HASH, GL_CHALLENGER_COMPACT = 1, 2, 4
 GL_PROVE_STAGES = 11
 GL_STARK_STAGES = 11
 STARK_STAGE_NAMES = ["trace commitment", "permutation zs", "zs commitment", "quotient polys", "quotient commitment", "opening set",
@@ -221,6 +242,12 @@ SIGNATURES = {
     "gl_stark_prove": (GlError, [_vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
     "gl_stark_permutation_zs": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "gl_stark_quotient_polys": (GlError, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gl_stark_tables_create": (GlError, [_u32, ctypes.POINTER(GlStarkTablesDesc), ctypes.POINTER(_vp), _vp]),
+    "gl_stark_tables_destroy": (None, [_vp]),
+    "gl_stark_tables_trim": (GlError, [_vp]),
+    "gl_stark_tables_prove": (GlError, [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
+    "gl_stark_tables_ctl_zs": (GlError, [_vp, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "gl_stark_tables_quotient_polys": (GlError, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

@@ -66,6 +66,12 @@ class Challenger:
         a, b = self.get_n_challenges(2)
         return (a, b)
 
+    def compact(self):  # challenger.rs:149-155
+        if self.input_buffer:
+            self.duplexing()
+        self.output_buffer = []
+        return list(self.sponge_state)
+
     def duplexing(self):  # challenger.rs:131-149
         for i, x in enumerate(self.input_buffer):
             self.sponge_state[i] = x
@@ -81,7 +87,7 @@ class DeviceChallenger:
     slots, observed as Challenger::observe_hash::<KeccakHash<25>> / observe_cap do: four elements per digest, its 25 bytes in
     chunks of 7, 7, 7 and 4 (hash/hash_types.rs:179-189)."""
 
-    RESET, HASH = 1, 2
+    RESET, HASH, COMPACT = 1, 2, 4
 
     def __init__(self, ctx):
         from .device import DeviceBuffer
@@ -99,9 +105,9 @@ class DeviceChallenger:
         ptr = buf if isinstance(buf, int) else buf.ptr
         return (ptr + 32 * first, 4 * n_digests, _lib.GL_OBSERVE_KECCAK_DIGESTS)
 
-    def step(self, srcs=(), n_challenges=0, hash_out=False, reset=False):
+    def step(self, srcs=(), n_challenges=0, hash_out=False, reset=False, compact=False):
         """observe `srcs`, then get_n_challenges(n_challenges) -> list of ints; hash_out: the 4 words of hash_n_to_hash_no_pad of
-        everything observed since the reset instead (use with reset=True)"""
+        everything observed since the reset instead (use with reset=True); compact: Challenger::compact() before observing"""
         import ctypes
 
         if n_challenges > 64:
@@ -110,7 +116,7 @@ class DeviceChallenger:
         for i, s in enumerate(srcs):
             p, count, planar = (tuple(s) + (0,))[:3]
             arr[i] = _lib.GlObserveSrc(p if isinstance(p, int) else p.ptr, count, planar)
-        flags = (self.RESET if reset or self._fresh else 0) | (self.HASH if hash_out else 0)
+        flags = (self.RESET if reset or self._fresh else 0) | (self.HASH if hash_out else 0) | (self.COMPACT if compact else 0)
         words = 4 if hash_out else n_challenges
         _lib.call("gl_challenger_step", self.state.ptr, ctypes.addressof(arr), len(srcs), n_challenges, self._out.ptr if words else None,
                   flags, self.ctx.ptr)

@@ -1113,8 +1113,12 @@ GlError gl_challenger_step(uint64_t *d_challenger, const GlObserveSrc *h_srcs, u
     DeviceCall device_call(ctx);
     if (!ctx || !d_challenger || (n_srcs && !h_srcs)) return fail(GL_E_INVALID, "null pointer");
     if (n_srcs > 8) return fail(GL_E_INVALID, "at most eight sources per step");
-    if (flags & ~(uint32_t)(GL_CHALLENGER_RESET | GL_CHALLENGER_HASH)) return fail(GL_E_INVALID, "unknown flag");
+    if (flags & ~(uint32_t)(GL_CHALLENGER_RESET | GL_CHALLENGER_HASH | GL_CHALLENGER_COMPACT)) return fail(GL_E_INVALID, "unknown flag");
     if (((flags & GL_CHALLENGER_HASH) || n_challenges) && !d_out) return fail(GL_E_INVALID, "null output");
+    // the kernel writes the outputs and then the transcript's words: an output inside the transcript would be overwritten, or corrupt it
+    const uint64_t out_words = (flags & GL_CHALLENGER_HASH) ? 4 : (n_challenges ? n_challenges : 1);
+    if (d_out && d_out + out_words > d_challenger && d_out < d_challenger + 32)
+        return fail(GL_E_INVALID, "d_out overlaps the 32 words of d_challenger");
     const uint64_t *ptrs[8];
     uint64_t counts[8], planar[8];
     for (uint32_t i = 0; i < n_srcs; i++) {

@@ -328,7 +328,7 @@ struct ChallengerArgs {
     ChallengerSrc src[8];
     uint32_t n_src, n_out, flags;
 };
-constexpr uint32_t CH_RESET = 1, CH_HASH = 2;
+constexpr uint32_t CH_RESET = 1, CH_HASH = 2, CH_COMPACT = 4;
 
 __global__ __launch_bounds__(64) void challenger_step_kernel(uint64_t *__restrict__ T, ChallengerArgs a, uint64_t *__restrict__ out,
                                                              poseidon_coop::Tables tb) {
@@ -338,6 +338,16 @@ __global__ __launch_bounds__(64) void challenger_step_kernel(uint64_t *__restric
     uint64_t x = (lane < 12 && !reset) ? T[lane] : 0;           // lane k < 12: state word k
     uint64_t inb = (lane < 8 && !reset) ? T[12 + lane] : 0;     // lane k < 8: input buffer slot k
     uint32_t in_len = reset ? 0u : (uint32_t)T[28], out_len = reset ? 0u : (uint32_t)T[29];
+    auto duplexing = [&]() {
+        if ((uint32_t)lane < in_len) x = inb;
+        x = poseidon_coop::permute(x, tb, lds);
+        in_len = 0;
+        out_len = 8;
+    };
+    if (a.flags & CH_COMPACT) {  // Challenger::compact (challenger.rs:149-155), before anything is observed
+        if (in_len) duplexing();
+        out_len = 0;
+    }
     uint64_t total = 0;
     for (uint32_t i = 0; i < a.n_src; i++) total += a.src[i].count;
     auto fetch = [&](uint64_t g) -> uint64_t {  // element g of the concatenated sources, canonical (observe_element takes field elements)
@@ -367,12 +377,6 @@ __global__ __launch_bounds__(64) void challenger_step_kernel(uint64_t *__restric
         in_len += r;
         out_len = 0;
     }
-    auto duplexing = [&]() {
-        if ((uint32_t)lane < in_len) x = inb;
-        x = poseidon_coop::permute(x, tb, lds);
-        in_len = 0;
-        out_len = 8;
-    };
     if (a.flags & CH_HASH) {
         // hash_n_to_hash_no_pad (hash/hashing.rs:81-108): a short last chunk overwrites its own words and is permuted; out = state[0..4)
         if (in_len) duplexing();

@@ -905,7 +905,8 @@ GlError gl_prove_zk(const void *circuit, const uint64_t *d_wires, const uint64_t
 
 }  // extern "C"
 
-// ---- STARKs: gl_stark_create / gl_stark_prove = starky's prove() (starky/src/prover.rs:32-195) --------------------------------------
+// ---- STARKs: gl_stark_create / gl_stark_prove = starky's prove() (starky/src/prover.rs:32-195); gl_stark_tables_create /
+// gl_stark_tables_prove = prove_with_traces (evm/src/prover.rs:66-421) over the same per-table flow ------------------------------------
 namespace {
 
 struct Stark : ProverShape {
@@ -921,9 +922,10 @@ struct Stark : ProverShape {
 
 GlError hip_fail(hipError_t e, const char *what) { return GlError{(int)e, strdup((std::string(what) + ": " + hipGetErrorString(e)).c_str())}; }
 
-// the quotient values of one trace, then their coset_ifft (prover.rs:314-318)
+// the quotient values of one trace, then their coset_ifft (prover.rs:314-318); ctl / h_ctl_challenges: the table's CTL checks, or null
 GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride, const uint64_t *h_alphas,
-                       const uint64_t *h_challenges, const uint64_t *d_public_inputs, uint64_t *d_out, void *ctx) {
+                       const uint64_t *h_challenges, const uint64_t *d_public_inputs, uint64_t *d_out, void *ctx,
+                       const plonky2_hip::StarkCtlDev *ctl = nullptr, const uint64_t *h_ctl_challenges = nullptr) {
     const plonky2_hip::NttTables *tb;
     if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
     plonky2_hip::StarkQuotientArgs a = {};
@@ -931,6 +933,7 @@ GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64
     a.trace_lde = d_trace_lde, a.zs_lde = d_zs_lde, a.column_stride = column_stride, a.pairs = s.pairs();
     a.alphas = h_alphas, a.challenges = h_challenges;
     a.num_challenges = s.num_challenges, a.qdf = s.qdf, a.degree_bits = s.degree_bits, a.rate_bits = s.rate_bits;
+    if (ctl) a.ctl = *ctl, a.ctl_challenges = h_ctl_challenges;
     const hipError_t e = plonky2_hip::stark_quotient_values(*tb, a, d_out, *reinterpret_cast<hipStream_t *>(ctx));
     if (e == hipErrorInvalidValue) return fail("inconsistent arguments of the STARK quotient (column_stride / challenges / sizes)");
     if (e != hipSuccess) return hip_fail(e, "stark_quotient_values");
@@ -938,12 +941,10 @@ GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64
     return gl_coset_ntt_batch(d_out, s.num_challenges, log_size, 1ull << log_size, 7, 1, ctx);
 }
 
-}  // namespace
-
-extern "C" {
-
-GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, void *ctx) {
-    if (!d || !stark || !ctx || !d->h_instrs || (d->num_immediates && !d->h_immediates) || (d->fri.num_reductions && !d->fri.reduction_arity_bits) ||
+// Everything gl_stark_create refuses, before anything is allocated. num_ctl_zs: the CTL Zs a table of
+// gl_stark_tables_create adds to the Zs oracle (0 for a STARK on its own).
+GlError stark_check(uint32_t hasher, const GlStarkDesc *d, uint32_t num_ctl_zs) {
+    if (!d || !d->h_instrs || (d->num_immediates && !d->h_immediates) || (d->fri.num_reductions && !d->fri.reduction_arity_bits) ||
         (d->num_pairs && (!d->h_column_pairs || !d->h_pair_bounds)))
         return fail("null pointer");
     if (d->struct_size != sizeof(GlStarkDesc))
@@ -962,13 +963,11 @@ GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, voi
     for (uint32_t li = 0; li < d->fri.num_reductions; li++) total_arity += d->fri.reduction_arity_bits[li];
     if (d->fri.cap_height > d->degree_bits + d->fri.rate_bits || total_arity > d->degree_bits + d->fri.rate_bits - d->fri.cap_height || total_arity > d->degree_bits)
         return fail("FRI total reduction arity is too large.");
-    uint32_t num_column_pairs = 0;
     if (d->num_pairs) {
         if (d->h_pair_bounds[0] != 0) return fail("h_pair_bounds must start at 0");
         for (uint32_t p = 0; p < d->num_pairs; p++)
             if (d->h_pair_bounds[p + 1] < d->h_pair_bounds[p]) return fail("h_pair_bounds must not decrease");
-        num_column_pairs = d->h_pair_bounds[d->num_pairs];
-        for (uint32_t k = 0; k < 2 * num_column_pairs; k++)
+        for (uint32_t k = 0; k < 2 * d->h_pair_bounds[d->num_pairs]; k++)
             if (d->h_column_pairs[k] >= d->num_columns) return fail("permutation pair: column out of range");
     }
     const uint32_t num_zs = d->num_pairs ? plonky2_hip::stark_num_zs(d->num_pairs, d->num_challenges, qdf) : 0;
@@ -982,7 +981,7 @@ GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, voi
         const struct {
             const char *name;
             uint32_t leaf_len;
-        } commitments[3] = {{"trace", d->num_columns}, {"permutation Zs", num_zs}, {"quotient", d->num_challenges * qdf}};
+        } commitments[3] = {{"trace", d->num_columns}, {num_ctl_zs ? "permutation / CTL Zs" : "permutation Zs", num_zs + num_ctl_zs}, {"quotient", d->num_challenges * qdf}};
         for (const auto &cm : commitments)
             if (cm.leaf_len == 4)
                 return fail(std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
@@ -992,12 +991,22 @@ GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, voi
                 return fail("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
                             " has arity_bits = 1: its leaves are 2 extension elements");
     }
+    return ok();
+}
+
+// after stark_check
+GlError stark_build(uint32_t hasher, const GlStarkDesc *d, Stark **stark, void *ctx) {
+    const uint32_t qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;
+    uint32_t qdb = 0;
+    while ((1u << qdb) < qdf) qdb++;
+    const uint32_t num_column_pairs = d->num_pairs ? d->h_pair_bounds[d->num_pairs] : 0;
     const plonky2_hip::NttTables *tb;  // makes the context's device current before the first allocation
     if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
     Stark *s = new Stark();
     s->hasher = hasher;
     s->degree_bits = d->degree_bits, s->num_columns = d->num_columns, s->num_public_inputs = d->num_public_inputs;
-    s->num_challenges = d->num_challenges, s->qdf = qdf, s->qdb = qdb, s->num_instrs = d->num_instrs, s->num_pairs = d->num_pairs, s->num_zs = num_zs;
+    s->num_challenges = d->num_challenges, s->qdf = qdf, s->qdb = qdb, s->num_instrs = d->num_instrs, s->num_pairs = d->num_pairs;
+    s->num_zs = d->num_pairs ? plonky2_hip::stark_num_zs(d->num_pairs, d->num_challenges, qdf) : 0;
     s->set_fri(d->fri);
     auto bail = [&](GlError e) {
         delete s;
@@ -1028,68 +1037,54 @@ GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, voi
     return ok();
 }
 
-void gl_stark_destroy(void *stark) { delete static_cast<Stark *>(stark); }
-
-GlError gl_stark_trim(void *stark) {
-    if (!stark) return fail("null pointer");
-    return static_cast<Stark *>(stark)->trim();
-}
-
-GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
-                                void *ctx) {
-    if (!stark || !d_trace || !h_challenges || !d_zs || !ctx) return fail("null pointer");
-    const Stark &s = *static_cast<const Stark *>(stark);
-    if (!s.num_pairs) return fail("the STARK has no permutation pairs");
-    if (trace_stride < (1ull << s.degree_bits)) return fail("trace_stride smaller than the column length");
-    const plonky2_hip::NttTables *tb;
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
-    const hipError_t e = plonky2_hip::stark_permutation_zs(*tb, d_trace, trace_stride, s.pairs(), h_challenges, s.num_challenges, s.qdf, s.degree_bits, d_zs,
-                                                           *reinterpret_cast<hipStream_t *>(ctx));
-    if (e != hipSuccess) return hip_fail(e, "stark_permutation_zs");
-    return ok();
-}
-
-GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
-                                const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
-                                uint64_t *d_quotient_polys, void *ctx) {
-    if (!stark || !d_trace_lde || !h_alphas || !d_quotient_polys || !ctx) return fail("null pointer");
-    const Stark &s = *static_cast<const Stark *>(stark);
-    if (s.num_pairs && (!d_zs_lde || !h_challenges)) return fail("the STARK has permutation pairs: d_zs_lde and h_challenges are needed");
-    if (s.num_public_inputs && !h_public_inputs) return fail("null public inputs");
-    if (column_stride < (1ull << (s.degree_bits + s.rate_bits))) return fail("column_stride smaller than the LDE's column length n << rate_bits");
-    const plonky2_hip::NttTables *tb;  // the context's device becomes current
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
-    DevBuf pis;
-    TRY(pis.alloc(s.num_public_inputs));
-    std::vector<uint64_t> h_pis(s.num_public_inputs);
-    for (uint32_t i = 0; i < s.num_public_inputs; i++) h_pis[i] = h_public_inputs[i] % P;
-    TRY(gl_memcpy_h2d(pis.p, h_pis.data(), 8ull * h_pis.size(), ctx));
-    TRY(stark_quotient(s, d_trace_lde, d_zs_lde, column_stride, h_alphas, h_challenges, pis.p, d_quotient_polys, ctx));
-    return gl_ctx_synchronize(ctx);  // pis is freed on return
-}
-
-GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_t *h_public_inputs, uint8_t **proof, uint64_t *proof_len,
-                       double *h_stage_ms, void *ctx) {
-    if (!stark || !d_trace || !proof || !proof_len || !ctx) return fail("null pointer");
-    const Stark &c = *static_cast<const Stark *>(stark);
-    if (c.num_public_inputs && !h_public_inputs) return fail("null public inputs");
-    {  // the context's device is current from here on, whatever the calling thread had: every allocation below follows it
-        const plonky2_hip::NttTables *tb;
-        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+// ---- the tables of gl_stark_tables_create: one Stark per table, the CTL descriptors in device memory ----
+struct StarkTables : ProverShape {  // a ProverShape for its pools: the trace commitments, the CTL Zs and the shared transcript of a proof
+    std::vector<Stark *> tables;
+    uint32_t num_challenges = 0;
+    DevBuf d_term_columns, d_term_coeffs, d_column_bounds, d_column_constants, d_twc_column_bounds, d_twc_filter;
+    std::vector<DevBuf> d_zs;          // per table: (twc, challenge) of its CTL Zs, in the order of cross_table_lookup_data
+    std::vector<uint32_t> num_ctl_zs;  // per table
+    ~StarkTables() {
+        for (Stark *s : tables) delete s;
     }
+    plonky2_hip::StarkCtlDev ctl(uint32_t k) const {
+        auto u32 = [](const DevBuf &b) { return reinterpret_cast<const uint32_t *>(b.p); };
+        plonky2_hip::StarkCtlDev c;
+        c.term_columns = u32(d_term_columns), c.column_bounds = u32(d_column_bounds), c.twc_column_bounds = u32(d_twc_column_bounds);
+        c.twc_filter = u32(d_twc_filter), c.zs = u32(d_zs[k]), c.term_coeffs = d_term_coeffs.p, c.column_constants = d_column_constants.p;
+        c.num_zs = num_ctl_zs[k];
+        return c;
+    }
+};
+
+// What a table of gl_stark_tables_prove brings to the flow of gl_stark_prove
+struct CtlPart {
+    Batch *trace;                     // committed before the transcript began
+    plonky2_hip::StarkCtlDev ctl;     // ctl.num_zs CTL Zs behind the permutation Zs
+    const uint64_t *d_ctl_zs;         // their values [ctl.num_zs][n]
+    const uint64_t *h_ctl_challenges;
+    uint64_t *d_transcript;           // the Challenger all tables share: compacted, never reset
+    const uint64_t *h_filter_flag;    // page-locked; its copy is queued: valid after the next host synchronisation
+};
+
+// One STARK proof from the trace (commitment) to its bytes, appended to `out`: prove() of starky/src/prover.rs:32-195 with a fresh
+// transcript and public inputs (ctl = null), or prove_single_table of evm/src/prover.rs:245-421 on the compacted shared transcript
+// with the table's CTL Zs in the Zs oracle, their checks in the quotient and the third opening batch.
+GlError stark_prove_one(const Stark &c, const uint64_t *d_trace, const uint64_t *h_public_inputs, const CtlPart *ctl, Bytes &out, double *h_stage_ms,
+                        void *ctx) {
     Pool *pool = c.pool_of(ctx);
     PoolScope pool_scope(pool);  // every DevBuf below comes from / returns to the handle's pool of this context
-    const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, qdb = c.qdb, npi = c.num_public_inputs, nz = c.num_zs;
+    const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, qdb = c.qdb, npi = c.num_public_inputs;
+    const uint32_t nperm = c.num_zs, nctl = ctl ? ctl->ctl.num_zs : 0, nz = nperm + nctl;
     const uint64_t n = 1ull << db, n_ext = n << c.rate_bits, cap_words = 4ull << c.cap_height;
-    const bool perm = c.num_pairs != 0;
-    if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_STARK_STAGES);
+    const bool perm = c.num_pairs != 0, has_zs = nz != 0;
     Stages st(h_stage_ms, ctx);
 
     // ---- the small-data side of the proof: one device buffer, one page-locked mirror ----
     // oracles: trace, [Zs], quotient (stark.rs:94-119)
     const uint32_t n_quot = nch * qdf;
     std::vector<uint32_t> leaf_len = {c.num_columns};
-    if (perm) leaf_len.push_back(nz);
+    if (has_zs) leaf_len.push_back(nz);
     leaf_len.push_back(n_quot);
     FriLayout L;
     TRY(fri_shapes(c, &L));
@@ -1097,9 +1092,10 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
     const Span T = sd.take(32), hostin = sd.take(npi);
     const Span fetch0 = sd.take(0);  // from here on: what the host fetches
     const Span perm_s = sd.take(perm ? 2ull * qdf * nch : 0), alphas_s = sd.take(nch), zeta_s = sd.take(2);
-    // openings at zeta and g * zeta: [2][n_polys] extension elements for the trace and the Zs, [1][n_polys] for the quotient
-    const Span open_trace = sd.take(4ull * c.num_columns), open_zs = sd.take(4ull * nz), open_quot = sd.take(2ull * n_quot);
-    const Span cap_trace = sd.take(cap_words), cap_zs = sd.take(perm ? cap_words : 0), cap_quot = sd.take(cap_words);
+    // openings at zeta and g * zeta: [2][n_polys] extension elements for the trace and the Zs, [1][n_polys] for the quotient; the CTL
+    // Zs at 1 / g as extension elements (x, 0)
+    const Span open_trace = sd.take(4ull * c.num_columns), open_zs = sd.take(4ull * nz), open_quot = sd.take(2ull * n_quot), open_last = sd.take(2ull * nctl);
+    const Span cap_trace = sd.take(cap_words), cap_zs = sd.take(has_zs ? cap_words : 0), cap_quot = sd.take(cap_words);
     fri_layout(c, leaf_len, &sd, &L);
     const uint64_t top = sd.top;
     DevBuf small;
@@ -1108,48 +1104,63 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
     uint64_t *H = nullptr;
     TRY(pool->staging(top, &H));
     auto fetch = [&](const Span &sp) { return copy_async(H + sp.off, D + sp.off, sp.words * 8, true, ctx); };
-    auto step = [&](std::initializer_list<GlObserveSrc> srcs, uint32_t n_out, const Span &out, uint32_t flags = 0) {
-        return gl_challenger_step(D + T.off, srcs.begin(), (uint32_t)srcs.size(), n_out, n_out ? D + out.off : nullptr, flags, ctx);
+    auto step = [&](std::initializer_list<GlObserveSrc> srcs, uint32_t n_out, const Span &out_s, uint32_t flags = 0) {
+        return gl_challenger_step(D + T.off, srcs.begin(), (uint32_t)srcs.size(), n_out, n_out ? D + out_s.off : nullptr, flags, ctx);
     };
     for (uint32_t i = 0; i < npi; i++) H[hostin.off + i] = h_public_inputs[i] % P;
     TRY(copy_async(D + hostin.off, H + hostin.off, hostin.words * 8, false, ctx));
 
     // trace commitment (prover.rs:57-70); the caller's trace stays intact
-    Batch trace;
-    {
+    Batch own_trace;
+    if (!ctl) {
         DevBuf w;
         TRY(w.alloc((uint64_t)c.num_columns * n));
         TRY(gl_memcpy_d2d(w.p, d_trace, 8ull * c.num_columns * n, ctx));
-        TRY(commit(&trace, std::move(w), true, c.num_columns, c, ctx, nullptr, false));
+        TRY(commit(&own_trace, std::move(w), true, c.num_columns, c, ctx, nullptr, false));
+    } else {
+        TRY(gl_memcpy_d2d(D + T.off, ctl->d_transcript, 32 * 8, ctx));  // the shared transcript runs on in this proof's buffer
     }
+    Batch &trace = ctl ? *ctl->trace : own_trace;
     TRY(st.mark(0));
-    // a fresh Challenger observes the trace cap (prover.rs:72-74), nothing else
+    // On its own: a fresh Challenger observes the trace cap (prover.rs:72-74), nothing else. As a table: the shared Challenger has
+    // observed every trace cap already and is compacted (evm/src/prover.rs:271).
+    const uint32_t begin = ctl ? GL_CHALLENGER_COMPACT : GL_CHALLENGER_RESET;
+    auto filter_check = [&]() { return ctl && *ctl->h_filter_flag ? fail("Non-binary filter?") : ok(); };
     Batch zs;
     std::vector<uint64_t> perm_challenges;
-    if (perm) {
-        // get_n_permutation_challenge_sets (permutation.rs:153-179): qdf sets of num_challenges (beta, gamma) draws
-        TRY(step({c.hashes(trace.cap_d.p, cap_words)}, 2 * qdf * nch, perm_s, GL_CHALLENGER_RESET));
-        TRY(fetch(perm_s));
-        TRY(stream_sync(ctx));
-        perm_challenges.assign(H + perm_s.off, H + perm_s.off + 2ull * qdf * nch);
+    if (has_zs) {
         DevBuf z;
         TRY(z.alloc((uint64_t)nz * n));
-        TRY(gl_stark_permutation_zs(stark, d_trace, n, perm_challenges.data(), z.p, ctx));
+        if (perm) {
+            // get_n_permutation_challenge_sets (permutation.rs:153-179): qdf sets of num_challenges (beta, gamma) draws
+            if (ctl)
+                TRY(step({}, 2 * qdf * nch, perm_s, begin));
+            else
+                TRY(step({c.hashes(trace.cap_d.p, cap_words)}, 2 * qdf * nch, perm_s, begin));
+            TRY(fetch(perm_s));
+            TRY(stream_sync(ctx));
+            TRY(filter_check());
+            perm_challenges.assign(H + perm_s.off, H + perm_s.off + 2ull * qdf * nch);
+            TRY(gl_stark_permutation_zs(&c, d_trace, n, perm_challenges.data(), z.p, ctx));
+        }
+        // the Zs oracle: permutation Zs, then CTL Zs (evm/src/prover.rs:290-311)
+        if (nctl) TRY(gl_memcpy_d2d(z.p + (uint64_t)nperm * n, ctl->d_ctl_zs, 8ull * nctl * n, ctx));
         TRY(st.mark(1));
         TRY(commit(&zs, std::move(z), true, nz, c, ctx, nullptr, false));
         TRY(st.mark(2));
-        TRY(step({c.hashes(zs.cap_d.p, cap_words)}, nch, alphas_s));
+        TRY(step({c.hashes(zs.cap_d.p, cap_words)}, nch, alphas_s, perm ? 0 : begin));
     } else {
-        TRY(step({c.hashes(trace.cap_d.p, cap_words)}, nch, alphas_s, GL_CHALLENGER_RESET));
+        TRY(step({c.hashes(trace.cap_d.p, cap_words)}, nch, alphas_s, begin));
     }
     TRY(fetch(alphas_s));
     TRY(stream_sync(ctx));
+    TRY(filter_check());
     const std::vector<uint64_t> alphas(H + alphas_s.off, H + alphas_s.off + nch);
     // quotient polynomials (prover.rs:115-123)
     DevBuf quotient;
     TRY(quotient.alloc((uint64_t)nch << (db + qdb)));
-    TRY(stark_quotient(c, trace.lde.p, perm ? zs.lde.p : nullptr, n_ext, alphas.data(), perm ? perm_challenges.data() : nullptr, D + hostin.off,
-                       quotient.p, ctx));
+    TRY(stark_quotient(c, trace.lde.p, has_zs ? zs.lde.p : nullptr, n_ext, alphas.data(), perm ? perm_challenges.data() : nullptr, D + hostin.off,
+                       quotient.p, ctx, ctl ? &ctl->ctl : nullptr, ctl ? ctl->h_ctl_challenges : nullptr));
     TRY(st.mark(3));
     // trim_to_len(degree * qdf) and the split into degree-n chunks (prover.rs:124-133), committed from coefficients. Of the
     // n << qdb coefficients those from qdf * n on must vanish: there are some only when qdf is no power of two.
@@ -1177,56 +1188,368 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
     const E2 zeta{H[zeta_s.off], H[zeta_s.off + 1]};
     if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail("Opening point is in the subgroup.");
     const uint64_t g = glh::root_of_unity(db);
-    const E2 g_zeta = e2_mul(E2{g, 0}, zeta);
-    // StarkOpeningSet::new (proof.rs:138-159): trace and Zs at zeta and g * zeta, the quotient at zeta
+    const E2 g_zeta = e2_mul(E2{g, 0}, zeta), g_inv{glh::inv(g), 0};
+    // StarkOpeningSet::new (proof.rs:138-159; evm/src/proof.rs:190-224): trace and Zs at zeta and g * zeta, the quotient at zeta, the
+    // CTL Zs at the last element of the subgroup
     {
-        const uint64_t pts[4] = {zeta.a, zeta.b, g_zeta.a, g_zeta.b};
+        const uint64_t pts[4] = {zeta.a, zeta.b, g_zeta.a, g_zeta.b}, last[2] = {g_inv.a, g_inv.b};
         TRY(gl_eval_polys_ext2(trace.coeffs.p, c.num_columns, db, n, pts, 2, D + open_trace.off, ctx));
-        if (perm) TRY(gl_eval_polys_ext2(zs.coeffs.p, nz, db, n, pts, 2, D + open_zs.off, ctx));
+        if (has_zs) TRY(gl_eval_polys_ext2(zs.coeffs.p, nz, db, n, pts, 2, D + open_zs.off, ctx));
         TRY(gl_eval_polys_ext2(quot.coeffs.p, n_quot, db, n, pts, 1, D + open_quot.off, ctx));
+        if (nctl) TRY(gl_eval_polys_ext2(zs.coeffs.p + (uint64_t)nperm * n, nctl, db, n, last, 1, D + open_last.off, ctx));
     }
     TRY(st.mark(5));
-    // to_fri_openings (proof.rs:161-182): [local_values, permutation_zs, quotient_polys], then [next_values, permutation_zs_next];
-    // the instance of stark.rs:88-137: batch 0 everything at zeta, batch 1 trace then Zs at g * zeta
+    // to_fri_openings (proof.rs:161-182): [local_values, permutation_zs, quotient_polys], then [next_values, permutation_zs_next], then
+    // with CTLs [ctl_zs_last]; the instance of stark.rs:88-137 (evm/src/stark.rs:83-142): batch 0 everything at zeta, batch 1 trace then
+    // Zs at g * zeta, batch 2 the CTL Zs at 1 / g
     std::vector<const Batch *> oracles = {&trace};
-    if (perm) oracles.push_back(&zs);
+    if (has_zs) oracles.push_back(&zs);
     oracles.push_back(&quot);
     uint64_t pow_witness = 0;
     {
-        std::vector<FriBatch> batches(2);
+        std::vector<FriBatch> batches(nctl ? 3 : 2);
         batches[0].point = zeta, batches[1].point = g_zeta;
         for (const Batch *o : oracles)
             for (uint32_t k = 0; k < o->n_polys; k++) batches[0].polys.push_back(o->coeffs.p + (uint64_t)k * n);
         for (size_t o = 0; o + 1 < oracles.size(); o++)
             for (uint32_t k = 0; k < oracles[o]->n_polys; k++) batches[1].polys.push_back(oracles[o]->coeffs.p + (uint64_t)k * n);
+        if (nctl) {
+            batches[2].point = g_inv;
+            for (uint32_t k = nperm; k < nz; k++) batches[2].polys.push_back(zs.coeffs.p + (uint64_t)k * n);
+        }
         std::vector<GlObserveSrc> srcs = {GlObserveSrc{D + open_trace.off, 2ull * c.num_columns, 0}};
-        if (perm) srcs.push_back(GlObserveSrc{D + open_zs.off, 2ull * nz, 0});
+        if (has_zs) srcs.push_back(GlObserveSrc{D + open_zs.off, 2ull * nz, 0});
         srcs.push_back(GlObserveSrc{D + open_quot.off, 2ull * n_quot, 0});
         srcs.push_back(GlObserveSrc{D + open_trace.off + 2ull * c.num_columns, 2ull * c.num_columns, 0});
-        if (perm) srcs.push_back(GlObserveSrc{D + open_zs.off + 2ull * nz, 2ull * nz, 0});
+        if (has_zs) srcs.push_back(GlObserveSrc{D + open_zs.off + 2ull * nz, 2ull * nz, 0});
+        if (nctl) srcs.push_back(GlObserveSrc{D + open_last.off, 2ull * nctl, 0});
         TRY(fri_prove(c, L, D, H, T, oracles, srcs, batches, st, &pow_witness, ctx));
     }
+    if (ctl) TRY(gl_memcpy_d2d(ctl->d_transcript, D + T.off, 32 * 8, ctx));  // the next table goes on from here
     // everything the proof consists of, in one go
     TRY(gl_memcpy_d2d(D + cap_trace.off, trace.cap_d.p, cap_words * 8, ctx));
-    if (perm) TRY(gl_memcpy_d2d(D + cap_zs.off, zs.cap_d.p, cap_words * 8, ctx));
+    if (has_zs) TRY(gl_memcpy_d2d(D + cap_zs.off, zs.cap_d.p, cap_words * 8, ctx));
     TRY(gl_memcpy_d2d(D + cap_quot.off, quot.cap_d.p, cap_words * 8, ctx));
     TRY(fetch(Span{fetch0.off, top - fetch0.off}));
     TRY(gl_ctx_synchronize(ctx));
     TRY(st.mark(9));
     TRY(fri_check_pow(c, L, H, pow_witness));
-    // ---- the wire format of StarkProofWithPublicInputs (include/plonky2_hip.h) ----
-    Bytes out;
+    // ---- the wire format of StarkProofWithPublicInputs / of one StarkProof of the tables (include/plonky2_hip.h) ----
     out.keccak = c.keccak();
     out.hashes(H + cap_trace.off, cap_words / 4);
-    if (perm) out.hashes(H + cap_zs.off, cap_words / 4);
+    if (has_zs) out.hashes(H + cap_zs.off, cap_words / 4);
     out.hashes(H + cap_quot.off, cap_words / 4);
     out.fields(H + open_trace.off, 4ull * c.num_columns);  // local_values, next_values
-    if (perm) out.fields(H + open_zs.off, 4ull * nz);      // permutation_zs, permutation_zs_next
+    if (has_zs) out.fields(H + open_zs.off, 4ull * nz);    // permutation_zs, permutation_zs_next
+    for (uint32_t k = 0; k < nctl; k++) out.field(H[open_last.off + 2ull * k]);  // ctl_zs_last: base field elements
     out.fields(H + open_quot.off, 2ull * n_quot);          // quotient_polys
     fri_write(out, c, L, H, oracles, pow_witness);
     out.fields(H + hostin.off, npi);
-    TRY(bytes_out(out, proof, proof_len));
     return st.mark(10);
+}
+
+}  // namespace
+
+extern "C" {
+
+GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, void *ctx) {
+    if (!d || !stark || !ctx) return fail("null pointer");
+    TRY(stark_check(hasher, d, 0));
+    Stark *s = nullptr;
+    TRY(stark_build(hasher, d, &s, ctx));
+    *stark = s;
+    return ok();
+}
+
+void gl_stark_destroy(void *stark) { delete static_cast<Stark *>(stark); }
+
+GlError gl_stark_trim(void *stark) {
+    if (!stark) return fail("null pointer");
+    return static_cast<Stark *>(stark)->trim();
+}
+
+GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
+                                void *ctx) {
+    if (!stark || !d_trace || !h_challenges || !d_zs || !ctx) return fail("null pointer");
+    const Stark &s = *static_cast<const Stark *>(stark);
+    if (!s.num_pairs) return fail("the STARK has no permutation pairs");
+    if (trace_stride < (1ull << s.degree_bits)) return fail("trace_stride smaller than the column length");
+    const plonky2_hip::NttTables *tb;
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    const hipError_t e = plonky2_hip::stark_permutation_zs(*tb, d_trace, trace_stride, s.pairs(), h_challenges, s.num_challenges, s.qdf, s.degree_bits, d_zs,
+                                                           *reinterpret_cast<hipStream_t *>(ctx));
+    if (e != hipSuccess) return hip_fail(e, "stark_permutation_zs");
+    return ok();
+}
+
+// gl_stark_quotient_polys, and with `ctl` gl_stark_tables_quotient_polys
+static GlError quotient_polys_call(const Stark &s, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride, const uint64_t *h_alphas,
+                                   const uint64_t *h_challenges, const uint64_t *h_public_inputs, uint64_t *d_quotient_polys, void *ctx,
+                                   const plonky2_hip::StarkCtlDev *ctl, const uint64_t *h_ctl_challenges) {
+    if (s.num_pairs && (!d_zs_lde || !h_challenges)) return fail("the STARK has permutation pairs: d_zs_lde and h_challenges are needed");
+    if (s.num_public_inputs && !h_public_inputs) return fail("null public inputs");
+    if (column_stride < (1ull << (s.degree_bits + s.rate_bits))) return fail("column_stride smaller than the LDE's column length n << rate_bits");
+    const plonky2_hip::NttTables *tb;  // the context's device becomes current
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    DevBuf pis;
+    TRY(pis.alloc(s.num_public_inputs));
+    std::vector<uint64_t> h_pis(s.num_public_inputs);
+    for (uint32_t i = 0; i < s.num_public_inputs; i++) h_pis[i] = h_public_inputs[i] % P;
+    TRY(gl_memcpy_h2d(pis.p, h_pis.data(), 8ull * h_pis.size(), ctx));
+    TRY(stark_quotient(s, d_trace_lde, d_zs_lde, column_stride, h_alphas, h_challenges, pis.p, d_quotient_polys, ctx, ctl, h_ctl_challenges));
+    return gl_ctx_synchronize(ctx);  // pis is freed on return
+}
+
+GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
+                                const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
+                                uint64_t *d_quotient_polys, void *ctx) {
+    if (!stark || !d_trace_lde || !h_alphas || !d_quotient_polys || !ctx) return fail("null pointer");
+    return quotient_polys_call(*static_cast<const Stark *>(stark), d_trace_lde, d_zs_lde, column_stride, h_alphas, h_challenges, h_public_inputs,
+                               d_quotient_polys, ctx, nullptr, nullptr);
+}
+
+GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_t *h_public_inputs, uint8_t **proof, uint64_t *proof_len,
+                       double *h_stage_ms, void *ctx) {
+    if (!stark || !d_trace || !proof || !proof_len || !ctx) return fail("null pointer");
+    const Stark &c = *static_cast<const Stark *>(stark);
+    if (c.num_public_inputs && !h_public_inputs) return fail("null public inputs");
+    {  // the context's device is current from here on, whatever the calling thread had: every allocation below follows it
+        const plonky2_hip::NttTables *tb;
+        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    }
+    if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_STARK_STAGES);
+    Bytes out;
+    TRY(stark_prove_one(c, d_trace, h_public_inputs, nullptr, out, h_stage_ms, ctx));
+    return bytes_out(out, proof, proof_len);
+}
+
+GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void **tables, void *ctx) {
+    if (!d || !tables || !ctx) return fail("null pointer");
+    if (d->struct_size != sizeof(GlStarkTablesDesc))
+        return fail("GlStarkTablesDesc.struct_size does not equal sizeof(GlStarkTablesDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+    if (!d->num_tables || !d->tables) return fail("no tables");
+    if (!d->num_lookups || !d->num_twcs || !d->h_lookup_bounds || !d->h_twc_table || !d->h_twc_column_bounds || !d->h_twc_filter || !d->h_column_bounds ||
+        (d->num_ctl_columns && !d->h_column_constants))
+        return fail("No CTL? (null or empty cross-table lookup arrays)");
+    const uint32_t nt = d->num_tables, ncol = d->num_ctl_columns, ntw = d->num_twcs, nl = d->num_lookups;
+    auto bounds_ok = [](const uint32_t *b, uint32_t count, uint32_t limit) {
+        if (b[0] != 0) return false;
+        for (uint32_t i = 0; i < count; i++)
+            if (b[i + 1] < b[i]) return false;
+        return b[count] <= limit;
+    };
+    if (!bounds_ok(d->h_column_bounds, ncol, 0xFFFFFFFFu)) return fail("h_column_bounds must start at 0 and not decrease");
+    const uint32_t nterms = d->h_column_bounds[ncol];
+    if (nterms && (!d->h_term_columns || !d->h_term_coeffs)) return fail("null pointer");
+    if (!bounds_ok(d->h_twc_column_bounds, ntw, ncol)) return fail("h_twc_column_bounds must start at 0, not decrease and stay within the CTL columns");
+    if (!bounds_ok(d->h_lookup_bounds, nl, ntw)) return fail("h_lookup_bounds must start at 0, not decrease and stay within the TWCs");
+    const uint32_t nch = d->tables[0].num_challenges;
+    for (uint32_t k = 0; k < nt; k++) {
+        const GlStarkDesc &t = d->tables[k], &t0 = d->tables[0];
+        if (t.struct_size != sizeof(GlStarkDesc)) return fail("GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+        if (t.num_challenges != t0.num_challenges || t.fri.rate_bits != t0.fri.rate_bits || t.fri.cap_height != t0.fri.cap_height ||
+            t.fri.proof_of_work_bits != t0.fri.proof_of_work_bits || t.fri.num_query_rounds != t0.fri.num_query_rounds || (t.fri.hiding != 0) != (t0.fri.hiding != 0))
+            return fail("table " + std::to_string(k) + ": the tables share one StarkConfig (num_challenges, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, hiding); only reduction_arity_bits may differ");
+        if (t.num_public_inputs) return fail("table " + std::to_string(k) + ": a table of a multi-table STARK has no public inputs");
+    }
+    // a CTL column as used by a TWC of table `table`: its terms name columns of that table
+    auto column_ok = [&](uint32_t col, uint32_t table) {
+        for (uint32_t j = d->h_column_bounds[col]; j < d->h_column_bounds[col + 1]; j++)
+            if (d->h_term_columns[j] >= d->tables[table].num_columns) return false;
+        return true;
+    };
+    for (uint32_t t = 0; t < ntw; t++) {
+        if (d->h_twc_table[t] >= nt) return fail("TWC " + std::to_string(t) + ": table out of range");
+        if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && d->h_twc_filter[t] >= ncol) return fail("TWC " + std::to_string(t) + ": filter column out of range");
+        for (uint32_t k = d->h_twc_column_bounds[t]; k < d->h_twc_column_bounds[t + 1]; k++)
+            if (!column_ok(k, d->h_twc_table[t])) return fail("TWC " + std::to_string(t) + ": a term's column is out of range for its table");
+        if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && !column_ok(d->h_twc_filter[t], d->h_twc_table[t]))
+            return fail("TWC " + std::to_string(t) + ": a term's column of the filter is out of range for its table");
+    }
+    std::vector<std::vector<uint32_t>> zs(nt);  // per table (twc, challenge), cross_table_lookup_data's order
+    std::vector<bool> filtered(nt, false), unfiltered(nt, false);
+    for (uint32_t l = 0; l < nl; l++) {
+        const uint32_t lo = d->h_lookup_bounds[l], hi = d->h_lookup_bounds[l + 1];
+        if (hi - lo < 2) return fail("lookup " + std::to_string(l) + ": a lookup has at least one looking table and the looked table");
+        const uint32_t width = d->h_twc_column_bounds[lo + 1] - d->h_twc_column_bounds[lo];
+        const bool has_filter = d->h_twc_filter[lo] != GL_CTL_NO_FILTER;
+        for (uint32_t t = lo; t < hi; t++) {
+            if (d->h_twc_column_bounds[t + 1] - d->h_twc_column_bounds[t] != width) return fail("lookup " + std::to_string(l) + ": its tables have unequal numbers of columns");
+            if ((d->h_twc_filter[t] != GL_CTL_NO_FILTER) != has_filter)
+                return fail("lookup " + std::to_string(l) + ": either every table of a lookup has a filter column or none has (CrossTableLookup::new)");
+            (has_filter ? filtered : unfiltered)[d->h_twc_table[t]] = true;
+        }
+        for (uint32_t c = 0; c < nch; c++)
+            for (uint32_t t = lo; t < hi; t++) zs[d->h_twc_table[t]].push_back(t), zs[d->h_twc_table[t]].push_back(c);
+    }
+    for (uint32_t k = 0; k < nt; k++) {
+        if (zs[k].empty()) return fail("No CTL? (no lookup names table " + std::to_string(k) + ")");
+        if (filtered[k] && d->tables[k].constraint_degree < 3) return fail("table " + std::to_string(k) + ": the checks of a filtered CTL Z have degree 3: constraint_degree must be at least 3");
+        if (d->tables[k].constraint_degree < 2) return fail("table " + std::to_string(k) + ": the checks of a CTL Z have degree 2: constraint_degree must be at least 2");
+        TRY(stark_check(hasher, &d->tables[k], (uint32_t)zs[k].size() / 2));
+    }
+    const plonky2_hip::NttTables *tb;
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    StarkTables *T = new StarkTables();
+    auto bail = [&](GlError e) {
+        delete T;
+        return e;
+    };
+#define STRY(expr)                         \
+    do {                                   \
+        GlError _e = (expr);               \
+        if (_e.code != 0) return bail(_e); \
+    } while (0)
+    T->hasher = hasher, T->num_challenges = nch;
+    T->set_fri(d->tables[0].fri);
+    for (uint32_t k = 0; k < nt; k++) {
+        Stark *s = nullptr;
+        STRY(stark_build(hasher, &d->tables[k], &s, ctx));
+        T->tables.push_back(s);
+    }
+    auto upload32 = [&](DevBuf &b, const uint32_t *src, uint64_t count) -> GlError {
+        TRY(b.alloc((count + 1) / 2));
+        return count ? gl_memcpy_h2d(b.p, src, 4 * count, ctx) : ok();
+    };
+    auto upload64 = [&](DevBuf &b, const uint64_t *src, uint64_t count) -> GlError {
+        std::vector<uint64_t> v(src, src + count);
+        for (uint64_t &x : v) x %= P;
+        TRY(b.alloc(count));
+        return count ? gl_memcpy_h2d(b.p, v.data(), 8 * count, ctx) : ok();
+    };
+    STRY(upload32(T->d_term_columns, d->h_term_columns, nterms));
+    STRY(upload64(T->d_term_coeffs, d->h_term_coeffs, nterms));
+    STRY(upload32(T->d_column_bounds, d->h_column_bounds, ncol + 1ull));
+    STRY(upload64(T->d_column_constants, d->h_column_constants, ncol));
+    STRY(upload32(T->d_twc_column_bounds, d->h_twc_column_bounds, ntw + 1ull));
+    STRY(upload32(T->d_twc_filter, d->h_twc_filter, ntw));
+    T->d_zs.resize(nt);
+    for (uint32_t k = 0; k < nt; k++) {
+        STRY(upload32(T->d_zs[k], zs[k].data(), zs[k].size()));
+        T->num_ctl_zs.push_back((uint32_t)zs[k].size() / 2);
+    }
+    STRY(gl_ctx_synchronize(ctx));
+#undef STRY
+    *tables = T;
+    return ok();
+}
+
+void gl_stark_tables_destroy(void *tables) { delete static_cast<StarkTables *>(tables); }
+
+GlError gl_stark_tables_trim(void *tables) {
+    if (!tables) return fail("null pointer");
+    StarkTables *T = static_cast<StarkTables *>(tables);
+    for (Stark *s : T->tables) TRY(s->trim());
+    return T->trim();
+}
+
+// the CTL Zs of table k; *d_flag is raised by a non-binary filter
+static GlError tables_ctl_zs(const StarkTables &T, uint32_t k, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_ctl_challenges,
+                             uint64_t *d_zs, uint64_t *d_flag, void *ctx) {
+    const plonky2_hip::NttTables *tb;
+    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    const hipError_t e = plonky2_hip::stark_ctl_zs(*tb, d_trace, trace_stride, T.ctl(k), h_ctl_challenges, T.num_challenges, T.tables[k]->degree_bits, d_zs,
+                                                   d_flag, *reinterpret_cast<hipStream_t *>(ctx));
+    if (e == hipErrorInvalidValue) return fail("inconsistent arguments of the CTL Zs (trace_stride / sizes / more Zs than the context's scratch holds block totals for)");
+    if (e != hipSuccess) return hip_fail(e, "stark_ctl_zs");
+    return ok();
+}
+
+GlError gl_stark_tables_ctl_zs(const void *tables, uint32_t table, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_ctl_challenges,
+                               uint64_t *d_zs, void *ctx) {
+    if (!tables || !d_trace || !h_ctl_challenges || !d_zs || !ctx) return fail("null pointer");
+    const StarkTables &T = *static_cast<const StarkTables *>(tables);
+    if (table >= T.tables.size()) return fail("table out of range");
+    if (trace_stride < (1ull << T.tables[table]->degree_bits)) return fail("trace_stride smaller than the column length");
+    {
+        const plonky2_hip::NttTables *tb;
+        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    }
+    DevBuf flag;
+    TRY(flag.alloc(1));
+    TRY(gl_memset_zero(flag.p, 8, ctx));
+    TRY(tables_ctl_zs(T, table, d_trace, trace_stride, h_ctl_challenges, d_zs, flag.p, ctx));
+    uint64_t h_flag = 0;
+    TRY(gl_memcpy_d2h(&h_flag, flag.p, 8, ctx));  // synchronous
+    if (h_flag) return fail("Non-binary filter?");
+    return ok();
+}
+
+GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde,
+                                       uint64_t column_stride, const uint64_t *h_alphas, const uint64_t *h_perm_challenges,
+                                       const uint64_t *h_ctl_challenges, uint64_t *d_quotient_polys, void *ctx) {
+    if (!tables || !d_trace_lde || !d_zs_lde || !h_alphas || !h_ctl_challenges || !d_quotient_polys || !ctx) return fail("null pointer");
+    const StarkTables &T = *static_cast<const StarkTables *>(tables);
+    if (table >= T.tables.size()) return fail("table out of range");
+    const plonky2_hip::StarkCtlDev ctl = T.ctl(table);
+    return quotient_polys_call(*T.tables[table], d_trace_lde, d_zs_lde, column_stride, h_alphas, h_perm_challenges, nullptr, d_quotient_polys, ctx, &ctl,
+                               h_ctl_challenges);
+}
+
+GlError gl_stark_tables_prove(const void *tables, const uint64_t *const *d_traces, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms,
+                              void *ctx) {
+    if (!tables || !d_traces || !proof || !proof_len || !ctx) return fail("null pointer");
+    const StarkTables &T = *static_cast<const StarkTables *>(tables);
+    const uint32_t nt = (uint32_t)T.tables.size(), nch = T.num_challenges;
+    for (uint32_t k = 0; k < nt; k++)
+        if (!d_traces[k]) return fail("null trace");
+    {
+        const plonky2_hip::NttTables *tb;
+        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    }
+    Pool *pool = T.pool_of(ctx);
+    PoolScope pool_scope(pool);  // the trace commitments, the CTL Zs and the shared small data; every table's own buffers: its Stark's pool
+    if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_STARK_STAGES * nt);
+    auto ms = [&](uint32_t k) { return h_stage_ms ? h_stage_ms + (size_t)GL_STARK_STAGES * k : nullptr; };
+    const uint64_t cap_words = 4ull << T.cap_height;
+    SmallData sd;
+    const Span TR = sd.take(32), chal_s = sd.take(2ull * nch), flag_s = sd.take(1);
+    DevBuf small;
+    TRY(small.alloc(sd.top));
+    uint64_t *const D = small.p;
+    uint64_t *H = nullptr;
+    TRY(pool->staging(sd.top, &H));
+    TRY(gl_memset_zero(D + flag_s.off, 8, ctx));
+    // every trace is committed before the transcript begins (evm/src/prover.rs:86-118) and stays until its table is proved
+    std::vector<Batch> traces(nt);
+    for (uint32_t k = 0; k < nt; k++) {
+        const Stark &c = *T.tables[k];
+        Stages st(ms(k), ctx);
+        DevBuf w;
+        TRY(w.alloc((uint64_t)c.num_columns << c.degree_bits));
+        TRY(gl_memcpy_d2d(w.p, d_traces[k], (8ull * c.num_columns) << c.degree_bits, ctx));
+        TRY(commit(&traces[k], std::move(w), true, c.num_columns, c, ctx, nullptr, false));
+        TRY(st.mark(0));
+    }
+    // a fresh Challenger observes all trace caps, then get_grand_product_challenge_set (cross_table_lookup.rs:243)
+    for (uint32_t k = 0; k < nt; k += 8) {
+        std::vector<GlObserveSrc> srcs;
+        for (uint32_t j = k; j < nt && j < k + 8; j++) srcs.push_back(T.hashes(traces[j].cap_d.p, cap_words));
+        const bool last = k + 8 >= nt;
+        TRY(gl_challenger_step(D + TR.off, srcs.data(), (uint32_t)srcs.size(), last ? 2 * nch : 0, last ? D + chal_s.off : nullptr,
+                               k == 0 ? GL_CHALLENGER_RESET : 0, ctx));
+    }
+    TRY(copy_async(H + chal_s.off, D + chal_s.off, chal_s.words * 8, true, ctx));
+    TRY(stream_sync(ctx));
+    const std::vector<uint64_t> ctl_challenges(H + chal_s.off, H + chal_s.off + 2ull * nch);
+    std::vector<DevBuf> ctl_zs(nt);
+    for (uint32_t k = 0; k < nt; k++) {
+        const Stark &c = *T.tables[k];
+        Stages st(ms(k), ctx);
+        TRY(ctl_zs[k].alloc((uint64_t)T.num_ctl_zs[k] << c.degree_bits));
+        TRY(tables_ctl_zs(T, k, d_traces[k], 1ull << c.degree_bits, ctl_challenges.data(), ctl_zs[k].p, D + flag_s.off, ctx));
+        TRY(st.mark(1));
+    }
+    H[flag_s.off] = 0;
+    TRY(copy_async(H + flag_s.off, D + flag_s.off, 8, true, ctx));  // read at the first table's first synchronisation
+    Bytes out;
+    for (uint32_t k = 0; k < nt; k++) {
+        CtlPart part{&traces[k], T.ctl(k), ctl_zs[k].p, ctl_challenges.data(), D + TR.off, H + flag_s.off};
+        TRY(stark_prove_one(*T.tables[k], d_traces[k], nullptr, &part, out, ms(k), ctx));
+        traces[k] = Batch();  // this table's trace LDE and CTL Zs return to the pool
+        ctl_zs[k].reset();
+    }
+    return bytes_out(out, proof, proof_len);
 }
 
 }  // extern "C"

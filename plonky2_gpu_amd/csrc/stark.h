@@ -38,6 +38,24 @@ hipError_t stark_permutation_zs(const NttTables &tb, const uint64_t *trace, uint
                                 const uint64_t *h_challenges, uint32_t num_challenges, uint32_t qdf, uint32_t log_n, uint64_t *out,
                                 hipStream_t stream);
 
+// The cross-table lookups seen from ONE table (evm/src/cross_table_lookup.rs), in device memory. A CTL column is
+// constant + sum_j coeff_j row[col_j] (Column::eval, :100-119): column k is the terms column_bounds[k] .. column_bounds[k + 1];
+// a table-with-columns (TWC) t is the CTL columns twc_column_bounds[t] .. twc_column_bounds[t + 1] with the filter column
+// twc_filter[t] or STARK_CTL_NO_FILTER. CTL Z number z of the table belongs to TWC zs[2 z] under challenge zs[2 z + 1], in the
+// order of cross_table_lookup_data (:237-312). Coefficients and constants are canonical.
+constexpr uint32_t STARK_CTL_NO_FILTER = 0xFFFFFFFFu;
+struct StarkCtlDev {
+    const uint32_t *term_columns = nullptr, *column_bounds = nullptr, *twc_column_bounds = nullptr, *twc_filter = nullptr, *zs = nullptr;
+    const uint64_t *term_coeffs = nullptr, *column_constants = nullptr;
+    uint32_t num_zs = 0;
+};
+
+// out: [ctl.num_zs][n] value columns, Z[i] = prod_{r <= i} s_r with s_r = gamma + sum_j beta^j column_j(row r) where the filter is
+// 1 and s_r = 1 where it is 0 (partial_products, cross_table_lookup.rs:314-341): the INCLUSIVE prefix product. h_challenges: (beta,
+// gamma) of challenge c at [2 c]. A filter value that is neither 0 nor 1 stores 1 into *d_flag (which the caller zeroes and reads).
+hipError_t stark_ctl_zs(const NttTables &tb, const uint64_t *trace, uint64_t trace_stride, const StarkCtlDev &ctl, const uint64_t *h_challenges,
+                        uint32_t num_challenges, uint32_t log_n, uint64_t *out, uint64_t *d_flag, hipStream_t stream);
+
 struct StarkQuotientArgs {
     const uint16_t *instrs;  // device, 4 x u16 per instruction
     uint32_t num_instrs;
@@ -48,6 +66,10 @@ struct StarkQuotientArgs {
     StarkPairsDev pairs;
     const uint64_t *alphas, *challenges;  // host
     uint32_t num_challenges, qdf, degree_bits, rate_bits;
+    // the CTL checks behind the permutation checks (eval_cross_table_lookup_checks, cross_table_lookup.rs:410-451): zs_lde holds the
+    // permutation Zs, then ctl.num_zs CTL Zs; ctl_challenges as for stark_ctl_zs (host). ctl.num_zs = 0: no CTL checks.
+    StarkCtlDev ctl;
+    const uint64_t *ctl_challenges;
 };
 
 // out: [num_challenges][n << log2_ceil(qdf)] quotient VALUES on the coset 7 * <w>, natural order (compute_quotient_polys,

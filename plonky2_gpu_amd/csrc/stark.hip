@@ -70,6 +70,72 @@ __device__ __forceinline__ void batch_products(const StarkPairsDev &pairs, const
     }
 }
 
+struct CtlChallenges {  // [challenge]
+    uint64_t beta[STARK_MAX_CHALLENGES], gamma[STARK_MAX_CHALLENGES];
+};
+
+// Column::eval (cross_table_lookup.rs:100-119) of CTL column k at one row; `row` points at the row's element of column 0. The
+// descriptors are read at wave-uniform addresses.
+__device__ __forceinline__ uint64_t ctl_column(const StarkCtlDev &d, uint32_t k, const uint64_t *row, uint64_t stride) {
+    uint64_t v = d.column_constants[k];
+    for (uint32_t j = d.column_bounds[k]; j < d.column_bounds[k + 1]; j++) v = gl::mac(v, row[d.term_columns[j] * stride], d.term_coeffs[j]);
+    return v;
+}
+
+// GrandProductChallenge::combine (evm/src/permutation.rs:61-73) over the columns of TWC t: gamma + sum_j beta^j column_j
+__device__ __forceinline__ uint64_t ctl_combine(const StarkCtlDev &d, uint32_t t, uint64_t beta, uint64_t gamma, const uint64_t *row, uint64_t stride) {
+    uint64_t acc = 0;
+    for (uint32_t k = d.twc_column_bounds[t + 1]; k-- > d.twc_column_bounds[t];) acc = gl::add(gl::mul(acc, beta), ctl_column(d, k, row, stride));
+    return gl::add(acc, gamma);
+}
+
+// challenge c of at most four, without indexing the kernel parameters by a register
+__device__ __forceinline__ void ctl_challenge(const CtlChallenges &ch, uint32_t c, uint64_t &beta, uint64_t &gamma) {
+    beta = ch.beta[0], gamma = ch.gamma[0];
+#pragma unroll
+    for (uint32_t e = 1; e < STARK_MAX_CHALLENGES; e++) {
+        beta = c == e ? ch.beta[e] : beta;
+        gamma = c == e ? ch.gamma[e] : gamma;
+    }
+}
+
+// the factor s_r of CTL Z number z at one row (partial_products, cross_table_lookup.rs:323-337): the filter is compared as a field
+// element; one that is neither 0 nor 1 raises *flag
+__device__ __forceinline__ uint64_t ctl_factor(const StarkCtlDev &d, const CtlChallenges &ch, uint32_t z, const uint64_t *row, uint64_t stride,
+                                               uint64_t *flag) {
+    const uint32_t t = d.zs[2 * z], filter = d.twc_filter[t];
+    uint64_t f = 1;
+    if (filter != STARK_CTL_NO_FILTER) f = gl::canon(ctl_column(d, filter, row, stride));
+    if (f > 1 && flag) *flag = 1;
+    if (f != 1) return 1;
+    uint64_t beta, gamma;
+    ctl_challenge(ch, d.zs[2 * z + 1], beta, gamma);
+    return ctl_combine(d, t, beta, gamma, row, stride);
+}
+
+// One thread per (row i, CTL Z z): the row's factor into the Z slot; the prefix product over the rows follows.
+__global__ __launch_bounds__(256) void stark_ctl_factors_kernel(const uint64_t *__restrict__ trace, uint64_t trace_stride, StarkCtlDev ctl,
+                                                                CtlChallenges ch, uint32_t log_n, uint64_t *__restrict__ out, uint64_t *flag) {
+    const uint64_t n = 1ull << log_n;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * ctl.num_zs) return;
+    out[g] = gl::canon(ctl_factor(ctl, ch, (uint32_t)(g >> log_n), trace + (g & (n - 1)), trace_stride, flag));
+}
+
+// The scan is exclusive and the CTL Zs are inclusive: Z[i] = (product of the earlier blocks) * (product of the block's earlier
+// rows) * s_i, with s_i evaluated once more (the scan overwrote it).
+__global__ __launch_bounds__(256) void stark_ctl_finalize_kernel(const uint64_t *__restrict__ trace, uint64_t trace_stride, StarkCtlDev ctl,
+                                                                 CtlChallenges ch, uint32_t log_n, uint64_t *out, const uint64_t *totals,
+                                                                 uint64_t totals_stride) {
+    const uint64_t n = 1ull << log_n;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * ctl.num_zs) return;
+    const uint64_t i = g & (n - 1);
+    const uint32_t z = (uint32_t)(g >> log_n);
+    const uint64_t s = ctl_factor(ctl, ch, z, trace + i, trace_stride, nullptr);
+    out[g] = gl::canon(gl::mul(gl::mul(out[g], totals[(uint64_t)z * totals_stride + i / SCAN_B]), s));
+}
+
 // One thread per (row i, Z polynomial b): the row's quotient numerator / denominator into the Z slot; the exclusive prefix
 // product over the rows follows (plonk_device.h). A zero denominator (the reference's batch inversion asserts) gives quotient 0.
 __global__ __launch_bounds__(256) void stark_perm_quotients_kernel(const uint64_t *__restrict__ trace, uint64_t trace_stride, StarkPairsDev pairs,
@@ -107,6 +173,8 @@ struct StarkQuotientParams {
     uint64_t alpha[STARK_MAX_CHALLENGES];
     uint64_t zh[16], zh_inv[16];  // Z_H on the coset takes 2^qdb values (field/src/zero_poly_coset.rs:20-41)
     PermChallenges ch;
+    StarkCtlDev ctl;  // num_zs = 0 without cross-table lookups
+    CtlChallenges ctl_ch;
 };
 
 __global__ __launch_bounds__(128) void stark_quotient_values_kernel(const StarkQuotientParams p) {
@@ -180,6 +248,23 @@ __global__ __launch_bounds__(128) void stark_quotient_values_kernel(const StarkQ
         batch_products(p.pairs, p.ch, p.num_challenges, p.qdf, z, local, p.stride, lhs, rhs);
         constraint(gl::sub(gl::mul(p.zs[z * p.stride + t_next], rhs), gl::mul(p.zs[z * p.stride + t], lhs)));
     }
+    // eval_cross_table_lookup_checks (evm/src/cross_table_lookup.rs:421-450), the CTL Zs behind the permutation Zs: with
+    // select(f, x) = f x + 1 - f, Z(1) = select(filter, combine) on the first row and Z(g x) = Z(x) select(filter', combine') on
+    // every row but the last
+    for (uint32_t z = 0; z < p.ctl.num_zs; z++) {
+        const uint32_t tw = p.ctl.zs[2 * z], filter = p.ctl.twc_filter[tw];
+        uint64_t beta, gamma;
+        ctl_challenge(p.ctl_ch, p.ctl.zs[2 * z + 1], beta, gamma);
+        uint64_t sel_local = ctl_combine(p.ctl, tw, beta, gamma, local, p.stride), sel_next = ctl_combine(p.ctl, tw, beta, gamma, next, p.stride);
+        if (filter != STARK_CTL_NO_FILTER) {
+            const uint64_t f_local = ctl_column(p.ctl, filter, local, p.stride), f_next = ctl_column(p.ctl, filter, next, p.stride);
+            sel_local = gl::sub(gl::mac(1, f_local, sel_local), f_local);
+            sel_next = gl::sub(gl::mac(1, f_next, sel_next), f_next);
+        }
+        const uint64_t z_local = p.zs[(p.num_zs + z) * p.stride + t], z_next = p.zs[(p.num_zs + z) * p.stride + t_next];
+        constraint(gl::mul(gl::sub(z_local, sel_local), l_first));
+        constraint(gl::mul(gl::sub(z_next, gl::mul(z_local, sel_next)), z_last));
+    }
 #pragma unroll
     for (uint32_t c = 0; c < STARK_MAX_CHALLENGES; c++)
         if (c < p.num_challenges) p.out[(uint64_t)c * size + i] = gl::canon(gl::mul(sums[c], zh_inv));  // prover.rs:296-302
@@ -192,6 +277,15 @@ bool load_challenges(PermChallenges *ch, const uint64_t *h_challenges, uint32_t 
     for (uint32_t k = 0; k < qdf * num_challenges; k++) {
         ch->beta[k] = h_challenges[2 * k] % glh::P;
         ch->gamma[k] = h_challenges[2 * k + 1] % glh::P;
+    }
+    return true;
+}
+
+bool load_ctl_challenges(CtlChallenges *ch, const uint64_t *h_challenges, uint32_t num_challenges) {
+    if (!h_challenges || num_challenges == 0 || num_challenges > STARK_MAX_CHALLENGES) return false;
+    for (uint32_t c = 0; c < num_challenges; c++) {
+        ch->beta[c] = h_challenges[2 * c] % glh::P;
+        ch->gamma[c] = h_challenges[2 * c + 1] % glh::P;
     }
     return true;
 }
@@ -269,6 +363,26 @@ hipError_t stark_permutation_zs(const NttTables &tb, const uint64_t *trace, uint
     return hipGetLastError();
 }
 
+hipError_t stark_ctl_zs(const NttTables &tb, const uint64_t *trace, uint64_t trace_stride, const StarkCtlDev &ctl, const uint64_t *h_challenges,
+                        uint32_t num_challenges, uint32_t log_n, uint64_t *out, uint64_t *d_flag, hipStream_t stream) {
+    CtlChallenges ch = {};
+    if (!load_ctl_challenges(&ch, h_challenges, num_challenges) || ctl.num_zs == 0 || log_n > 24 || trace_stride < (1ull << log_n))
+        return hipErrorInvalidValue;
+    const uint64_t n = 1ull << log_n;
+    const uint64_t blocks = (n + SCAN_B - 1) / SCAN_B;
+    if (!tb.scratch || tb.scratch_elems < blocks * ctl.num_zs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stark_ctl_factors_kernel, dim3(grid_for(n * ctl.num_zs, 256)), dim3(256), 0, stream, trace, trace_stride, ctl, ch, log_n, out,
+                       d_flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    uint64_t *totals = tb.scratch;
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)blocks, ctl.num_zs), dim3(SCAN_T), 0, stream, out, n, n, totals, blocks);
+    hipLaunchKernelGGL(scan_totals_kernel, dim3(ctl.num_zs), dim3(SCAN_T), 0, stream, totals, blocks, blocks);
+    hipLaunchKernelGGL(stark_ctl_finalize_kernel, dim3(grid_for(n * ctl.num_zs, 256)), dim3(256), 0, stream, trace, trace_stride, ctl, ch, log_n, out,
+                       totals, blocks);
+    return hipGetLastError();
+}
+
 hipError_t stark_quotient_values(const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream) {
     uint32_t qdb = 0;
     while ((1u << qdb) < a.qdf) qdb++;  // log2_ceil
@@ -283,6 +397,10 @@ hipError_t stark_quotient_values(const NttTables &tb, const StarkQuotientArgs &a
         if (!a.zs_lde || !a.challenges || !load_challenges(&p.ch, a.challenges, a.num_challenges, a.qdf)) return hipErrorInvalidValue;
         p.pairs = a.pairs;
         p.num_zs = stark_num_zs(a.pairs.num_pairs, a.num_challenges, a.qdf);
+    }
+    if (a.ctl.num_zs) {
+        if (!a.zs_lde || !load_ctl_challenges(&p.ctl_ch, a.ctl_challenges, a.num_challenges)) return hipErrorInvalidValue;
+        p.ctl = a.ctl;
     }
     p.shift = 7;
     p.g_inv = glh::inv(glh::root_of_unity(a.degree_bits));

@@ -11,7 +11,14 @@ are timed by the wall clock around gl_stark_prove (it ends synchronised); median
 further proof. Oracle-free: every proof must equal the first one and round-trip through the wire format. One JSON line on stdout
 (and --out, by default profiles/stark_prove.json).
 
-  python tools/bench_stark_prove.py [--min-bits 16] [--max-bits 20] [--reps 7] [--out profiles/stark_prove.json]"""
+  python tools/bench_stark_prove.py [--min-bits 16] [--max-bits 20] [--reps 7] [--out profiles/stark_prove.json]
+
+The shape `ctl` (--shapes ctl, not among the defaults) is a multi-table STARK (gl_stark_tables_create / gl_stark_tables_prove): three
+tables of 100, 30 and 8 columns at 2^18, 2^16 and 2^14 rows, degree 3, tied by four cross-table lookups, each table under
+standard_fast_config at its own size. In the same run the three tables are also proved one by one with gl_stark_prove, without their
+lookups; the result — per-table stage times, both totals and their ratio — goes to --ctl-out (profiles/stark_ctl_prove.json).
+
+  python tools/bench_stark_prove.py --shapes ctl [--reps 7] [--ctl-out profiles/stark_ctl_prove.json]"""
 import argparse
 import json
 import os
@@ -118,6 +125,94 @@ def measure(ctx, make, degree_bits, reps, hasher="poseidon"):
             "columns": desc.num_columns, "stage_ms": stages, "largest_stage": max(stages, key=stages.get)}
 
 
+CTL_TABLES = ((100, 18), (30, 16), (8, 14))  # (columns, degree_bits)
+
+
+def ctl_table(ctx, columns, degree_bits, flags):
+    """(program, trace in HBM) of one table: c0 counts from 5, then triples (a, b, c) with c = a * b * c0 (degree 3), then one
+    binary flag column per entry of `flags` (1 on the first 2^flag rows), then free columns"""
+    triples = (columns - 1 - len(flags)) // 3
+    a = pstark.StarkAsm()
+    a.emit_first_row(a.sub(a.local(0), a.imm(5)))
+    a.emit_transition(a.sub(a.next(0), a.add(a.local(0), a.imm(1))))
+    for j in range(triples):
+        a.release()
+        a.emit(a.sub(a.local(3 + 3 * j), a.mul(a.mul(a.local(1 + 3 * j), a.local(2 + 3 * j)), a.local(0))))
+    for k in range(len(flags)):
+        a.release()
+        f = a.local(1 + 3 * triples + k)
+        a.emit(a.mul(f, a.sub(f, a.imm(1))))
+    n = 1 << degree_bits
+    trace = np.random.default_rng(columns).integers(0, P, size=(columns, n), dtype=np.uint64)
+    trace[0] = np.arange(5, n + 5, dtype=np.uint64)
+    for k, bits in enumerate(flags):
+        trace[1 + 3 * triples + k] = (np.arange(n) < (1 << bits)).astype(np.uint64)
+    d_trace = pg.DeviceBuffer.from_host(ctx, trace)
+    for j in range(triples):
+        out = d_trace.at((3 + 3 * j) * n)
+        _lib.call("gl_debug_field_op", 2, d_trace.at((1 + 3 * j) * n), d_trace.at((2 + 3 * j) * n), out, n, ctx.ptr)
+        _lib.call("gl_debug_field_op", 2, out, d_trace.at(0), out, n, ctx.ptr)
+    ctx.synchronize()
+    return a.program(), d_trace, 1 + 3 * triples
+
+
+def measure_ctl(ctx, reps, hasher="poseidon"):
+    """Four lookups, all of them satisfied: the first 2^14 counters of tables 0 and 1 into table 2 and the first 2^16 counters of
+    table 0 into table 1 (filtered on the looking side by a flag column, on the looked side by the constant 1), and table 2 into
+    itself without filters over two columns: 4, 4 and 8 CTL Zs."""
+    Col, Twc, Lookup = pstark.CtlColumn, pstark.TableWithColumns, pstark.CrossTableLookup
+    flags = ((14, 16), (14,), ())
+    built = [ctl_table(ctx, cols, db, fl) for (cols, db), fl in zip(CTL_TABLES, flags)]
+    descs = [pstark.StarkDesc(db, cols, 0, 3, 2, fast_config_fri_params(db), prog[0], prog[1], [])
+             for (cols, db), (prog, _, _) in zip(CTL_TABLES, built)]
+    f0, f1 = built[0][2], built[1][2]  # the first flag column of tables 0 and 1
+    one, counter = Col.constant(1), [Col.single(0)]
+    both = [Col.single(0), Col.linear_combination([(0, 2)], 1)]
+    lookups = [Lookup([Twc(0, counter, Col.single(f0))], Twc(2, counter, one)), Lookup([Twc(1, counter, Col.single(f1))], Twc(2, counter, one)),
+               Lookup([Twc(0, counter, Col.single(f0 + 1))], Twc(1, counter, one)), Lookup([Twc(2, both)], Twc(2, both))]
+    desc = pstark.StarkTablesDesc(descs, lookups)
+    desc.validate(hasher)
+    traces = [d for _, d, _ in built]
+
+    def timed(fn):
+        first = fn()
+        fn()
+        ms = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            data = fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            if data != first:
+                raise SystemExit("bench_stark_prove: the proof is not deterministic")
+        return first, {"median_ms": round(float(np.median(ms)), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+    nt = pg.NativeStarkTables(ctx, desc, hasher)
+    first, res = timed(lambda: nt.prove_bytes(traces))
+    if pstark.tables_proof_to_bytes(pstark.tables_proof_from_bytes(first, desc, hasher), desc, hasher) != first:
+        raise SystemExit("bench_stark_prove: the proof does not round-trip through the wire format")
+    timing = []
+    nt.prove_bytes(traces, timing=timing)
+    nt.close()
+    res["proof_bytes"] = len(first)
+    res["tables"] = [{"columns": cols, "degree_bits": db, "ctl_zs": desc.num_ctl_zs(k), "stage_ms": {s: round(v, 3) for s, v in timing[k].items()},
+                      "total_ms": round(sum(timing[k].values()), 3)} for k, (cols, db) in enumerate(CTL_TABLES)]
+    alone = []
+    for d, d_trace in zip(descs, traces):  # the same tables without their lookups, one gl_stark_prove each
+        ns = pg.NativeStark(ctx, d, hasher)
+        stages = {}
+        _, r = timed(lambda: ns.prove_bytes(d_trace, []))
+        ns.prove_bytes(d_trace, [], stages)
+        ns.close()
+        r["stage_ms"] = {s: round(v, 3) for s, v in stages.items()}
+        alone.append(r)
+    for d_trace in traces:
+        d_trace.free()
+    res["without_lookups"] = alone
+    res["without_lookups_sum_median_ms"] = round(sum(r["median_ms"] for r in alone), 3)
+    res["ratio"] = round(res["median_ms"] / res["without_lookups_sum_median_ms"], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--min-bits", type=int, default=16)
@@ -125,6 +220,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shapes", default="fibonacci,wide")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stark_prove.json"))
+    ap.add_argument("--ctl-out", default=os.path.join(ROOT, "profiles", "stark_ctl_prove.json"))
     a = ap.parse_args()
     if a.reps < 1 or not 6 <= a.min_bits <= a.max_bits <= 22:
         ap.error("--reps >= 1 and 6 <= --min-bits <= --max-bits <= 22")
@@ -132,7 +228,21 @@ def main():
     res = {"tool": "tools/bench_stark_prove.py", "library": _lib.load().gl_version().decode(), "hasher": "poseidon", "reps": a.reps,
            "config": "standard_fast_config: 2 challenges, rate_bits 1, cap_height 4, 16 PoW bits, arity 4 down to 2^5, 84 queries; trace resident"}
     makers = {"fibonacci": fibonacci, "wide": wide}
-    for shape in a.shapes.split(","):
+    shapes = a.shapes.split(",")
+    if "ctl" in shapes:
+        shapes.remove("ctl")
+        ctl = dict(res, shape="three tables of 100, 30 and 8 columns at 2^18, 2^16 and 2^14 rows, degree 3, four cross-table lookups",
+                   **measure_ctl(ctx, a.reps))
+        line = json.dumps(ctl)
+        if a.ctl_out:
+            os.makedirs(os.path.dirname(a.ctl_out), exist_ok=True)
+            with open(a.ctl_out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+    if not shapes:
+        ctx.close()
+        return
+    for shape in shapes:
         res[shape] = {}
         for bits in range(a.min_bits, a.max_bits + 1):
             res[shape]["2^%d" % bits] = measure(ctx, makers[shape], bits, a.reps)
