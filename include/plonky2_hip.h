@@ -721,6 +721,34 @@ GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const
                                        const uint64_t *h_ctl_challenges, uint64_t *d_quotient_polys, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The lookup columns of a trace: the Halo2-style lookup argument of the reference's STARKs (evm/src/lookup.rs, used by its memory
+ * table, memory_stark.rs:147, and by system_zero/src/lookup.rs). A lookup is four trace columns: the inputs, the table, and the
+ * two columns that permuted_cols(inputs, table) (lookup.rs:67-131) fills. The constraints are eval_lookups (lookup.rs:13-34: a
+ * program of LOAD_WIRE / LOAD_NEXT / SUB / MUL / EMIT / EMIT_LAST_ROW) and the two permutation pairs (input, permuted input) and
+ * (table, permuted table) (memory_stark.rs:452-456). CONTRACT: inputs may be any u64 representatives, n is any length with
+ * 1 <= n <= 2^30 (no power of two needed); every output is canonical; permuted_inputs is the inputs' canonical values in ascending
+ * order; permuted_table is EXACTLY the reference's column, bit for bit: beside the first input of a run of equal values that the
+ * table holds stands that value, and an input the table does not hold gets the table value the reference's serial merge gives it
+ * — the unused table value pushed LAST before it (its stack is LIFO), or, where that stack is empty or the merge has ended, the
+ * values left on the stack from the bottom, in order.
+ * Everything runs on ctx->stream in call order and returns without waiting; nothing is allocated: the caller provides d_scratch
+ * of gl_lookup_scratch_bytes(n) bytes (about 8.7 n words), 16-byte aligned, which holds nothing between calls. Refused with
+ * GL_E_INVALID before anything is launched: n out of range, NULL pointers, an output that overlaps an input or the other output
+ * (gl_sort_canonical: d_out == d_in is allowed, a partial overlap is not), and for gl_stark_fill_lookups a column index
+ * >= num_columns, trace_stride < n, and a permuted column that is also an input, table or permuted column of a lookup of the call.
+ * ------------------------------------------------------------------------------------------- */
+uint64_t gl_lookup_scratch_bytes(uint64_t n);
+/* canonical values of d_in[0..n) in ascending order -> d_out (d_out == d_in allowed) */
+GlError gl_sort_canonical(const uint64_t *d_in, uint64_t *d_out, uint64_t n, void *d_scratch, void *ctx);
+/* permuted_cols (evm/src/lookup.rs:67-131), bit for bit */
+GlError gl_lookup_permuted_cols(const uint64_t *d_inputs, const uint64_t *d_table, uint64_t n, uint64_t *d_permuted_inputs,
+                                uint64_t *d_permuted_table, void *d_scratch, void *ctx);
+/* h_lookups: 4 words per lookup (input, table, permuted input, permuted table): columns of d_trace [num_columns][pitch trace_stride
+ * >= n]; the two permuted columns are written, everything else is left untouched */
+GlError gl_stark_fill_lookups(uint64_t *d_trace, uint64_t trace_stride, uint64_t n, uint32_t num_columns, const uint32_t *h_lookups,
+                              uint32_t num_lookups, void *d_scratch, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

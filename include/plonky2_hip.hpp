@@ -7,6 +7,7 @@
 // Host containers are std::vector<uint64_t>; everything else stays in HBM. Errors (the reference
 // panics or drops them) become plonky2_hip::Error exceptions. No CPU fallback exists.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <stdexcept>
@@ -373,5 +374,14 @@ class StarkTables {
     void *ptr_ = nullptr;
     uint32_t num_tables_;
 };
+
+// The lookup columns of a trace (plonky2_hip.h "The lookup columns of a trace"). d_scratch: gl_lookup_scratch_bytes(n) bytes in HBM.
+// lookups: (input, table, permuted input, permuted table) columns of d_trace; the two permuted columns are written on the
+// context's stream, before a prove() of the same context reads them.
+inline void fill_lookups(const Context &ctx, uint64_t *d_trace, uint64_t trace_stride, uint64_t n, uint32_t num_columns,
+                         const std::vector<std::array<uint32_t, 4>> &lookups, void *d_scratch) {
+    check(gl_stark_fill_lookups(d_trace, trace_stride, n, num_columns, lookups.empty() ? nullptr : lookups[0].data(), (uint32_t)lookups.size(),
+                                d_scratch, ctx.get()));
+}
 
 }  // namespace plonky2_hip

@@ -18,7 +18,7 @@ from . import serialization  # noqa: F401
 from .fri import prove_openings  # noqa: F401
 from .prover import CircuitData, GateProgram, NativeCircuit, all_wires_permutation_partial_products, compute_quotient_polys, prove  # noqa: F401
 from .prover import reference_compute_quotient_polys, reference_set_public_inputs_hash  # noqa: F401
-from . import stark  # noqa: F401
+from . import lookup, stark  # noqa: F401
 from .stark import CrossTableLookup, CtlColumn, NativeStark, NativeStarkTables, StarkAsm, StarkDesc, StarkTablesDesc, TableWithColumns  # noqa: F401
 
 P = 0xFFFFFFFF00000001

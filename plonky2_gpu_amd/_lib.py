@@ -248,6 +248,10 @@ SIGNATURES = {
     "gl_stark_tables_prove": (GlError, [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
     "gl_stark_tables_ctl_zs": (GlError, [_vp, _u32, _vp, _u64, _vp, _vp, _vp]),
     "gl_stark_tables_quotient_polys": (GlError, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gl_lookup_scratch_bytes": (_u64, [_u64]),
+    "gl_sort_canonical": (GlError, [_vp, _vp, _u64, _vp, _vp]),
+    "gl_lookup_permuted_cols": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "gl_stark_fill_lookups": (GlError, [_vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

@@ -19,6 +19,7 @@
 #include "ntt_kernels.h"
 #include "plonk.h"
 #include "stark.h"
+#include "lookup.h"
 #include "fri.h"
 #include "ed25519_gate_program.inc"
 
@@ -1324,6 +1325,68 @@ GlError gl_commit_from_values_h(uint32_t hasher, uint64_t *d_values, uint64_t po
     GlError e = gl_ntt_batch(d_values, poly_num, log_n, 1ull << log_n, 1, 0, ctx);
     if (e.code) return e;
     return gl_commit_from_coeffs_h(hasher, d_values, poly_num, log_n, rate_bits, cap_height, salt_size, shift, d_lde, d_leaves, d_digests, d_cap, ctx);
+}
+
+// ---------------------------------------------------------------- the lookup columns of a trace (lookup.hip)
+static bool words_overlap(const uint64_t *a, const uint64_t *b, uint64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 8;
+    return x < y + bytes && y < x + bytes;
+}
+
+static const char *lookup_argument_error(uint64_t n, const void *d_scratch, const void *ctx) {
+    if (n < 1 || n > LOOKUP_MAX_N) return "n must be in 1 ..= 2^30";
+    if (!d_scratch || !ctx) return "null pointer";
+    if ((uintptr_t)d_scratch & 15) return "d_scratch must be 16-byte aligned";
+    return nullptr;
+}
+
+uint64_t gl_lookup_scratch_bytes(uint64_t n) {
+    if (n < 1 || n > LOOKUP_MAX_N) return 0;
+    return lookup_scratch_layout(nullptr, n).words * 8;
+}
+
+GlError gl_sort_canonical(const uint64_t *d_in, uint64_t *d_out, uint64_t n, void *d_scratch, void *ctx) {
+    DeviceCall device_call(ctx);
+    if (const char *why = lookup_argument_error(n, d_scratch, ctx)) return fail(GL_E_INVALID, std::string("gl_sort_canonical: ") + why);
+    if (!d_in || !d_out) return fail(GL_E_INVALID, "gl_sort_canonical: null pointer");
+    if (d_in != d_out && words_overlap(d_in, d_out, n)) return fail(GL_E_INVALID, "gl_sort_canonical: d_out overlaps d_in without being d_in");
+    HIP_TRY(lookup_sort_canonical(d_in, d_out, n, lookup_scratch_layout(d_scratch, n), S(ctx)->stream));
+    return ok();
+}
+
+GlError gl_lookup_permuted_cols(const uint64_t *d_inputs, const uint64_t *d_table, uint64_t n, uint64_t *d_permuted_inputs,
+                                uint64_t *d_permuted_table, void *d_scratch, void *ctx) {
+    DeviceCall device_call(ctx);
+    if (const char *why = lookup_argument_error(n, d_scratch, ctx)) return fail(GL_E_INVALID, std::string("gl_lookup_permuted_cols: ") + why);
+    if (!d_inputs || !d_table || !d_permuted_inputs || !d_permuted_table) return fail(GL_E_INVALID, "gl_lookup_permuted_cols: null pointer");
+    if (words_overlap(d_permuted_inputs, d_permuted_table, n)) return fail(GL_E_INVALID, "gl_lookup_permuted_cols: the two outputs overlap");
+    for (const uint64_t *out : {d_permuted_inputs, d_permuted_table})
+        if (words_overlap(out, d_inputs, n) || words_overlap(out, d_table, n))
+            return fail(GL_E_INVALID, "gl_lookup_permuted_cols: an output overlaps an input");
+    HIP_TRY(lookup_permuted_cols(d_inputs, d_table, n, d_permuted_inputs, d_permuted_table, lookup_scratch_layout(d_scratch, n), S(ctx)->stream));
+    return ok();
+}
+
+GlError gl_stark_fill_lookups(uint64_t *d_trace, uint64_t trace_stride, uint64_t n, uint32_t num_columns, const uint32_t *h_lookups,
+                              uint32_t num_lookups, void *d_scratch, void *ctx) {
+    DeviceCall device_call(ctx);
+    if (const char *why = lookup_argument_error(n, d_scratch, ctx)) return fail(GL_E_INVALID, std::string("gl_stark_fill_lookups: ") + why);
+    if (!d_trace || (!h_lookups && num_lookups)) return fail(GL_E_INVALID, "gl_stark_fill_lookups: null pointer");
+    if (trace_stride < n) return fail(GL_E_INVALID, "gl_stark_fill_lookups: trace_stride smaller than n: the columns would overlap");
+    for (uint32_t i = 0; i < 4 * num_lookups; ++i)
+        if (h_lookups[i] >= num_columns) return fail(GL_E_INVALID, "gl_stark_fill_lookups: column out of range");
+    for (uint32_t l = 0; l < num_lookups; ++l)
+        for (uint32_t w = 2; w < 4; ++w)  // a column this call writes is no other column of the call
+            for (uint32_t i = 0; i < 4 * num_lookups; ++i)
+                if (i != 4 * l + w && h_lookups[i] == h_lookups[4 * l + w])
+                    return fail(GL_E_INVALID, "gl_stark_fill_lookups: a permuted column is also an input, table or permuted column of the call");
+    const LookupScratch scratch = lookup_scratch_layout(d_scratch, n);
+    for (uint32_t l = 0; l < num_lookups; ++l) {
+        const uint32_t *c = h_lookups + 4 * l;
+        HIP_TRY(lookup_permuted_cols(d_trace + c[0] * trace_stride, d_trace + c[1] * trace_stride, n, d_trace + c[2] * trace_stride,
+                                     d_trace + c[3] * trace_stride, scratch, S(ctx)->stream));
+    }
+    return ok();
 }
 
 GlError gl_debug_copy(void *d_dst, const void *d_src, uint64_t bytes, void *ctx) {

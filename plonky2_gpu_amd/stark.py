@@ -56,6 +56,17 @@ class StarkAsm(GateAsm):
     def emit_last_row(self, a):
         self.instrs.append((EMIT_LAST_ROW, 0, a, 0))
 
+    def eval_lookups(self, col_permuted_input, col_permuted_table):
+        """eval_lookups (evm/src/lookup.rs:19-33): the constraints of one lookup whose permuted columns plonky2_gpu_amd.lookup
+        fills. constraint_last_row of the next row's difference constrains the first row."""
+        local_perm_input = self.local(col_permuted_input)
+        next_perm_table = self.next(col_permuted_table)
+        next_perm_input = self.next(col_permuted_input)
+        diff_input_prev = self.sub(next_perm_input, local_perm_input)
+        diff_input_table = self.sub(next_perm_input, next_perm_table)
+        self.emit(self.mul(diff_input_prev, diff_input_table))
+        self.emit_last_row(diff_input_table)
+
     def program(self):
         """(instrs [k][4] uint16, immediates list)"""
         return np.array(self.instrs, dtype=np.uint16).reshape(-1, 4), list(self.pool.values)
