@@ -28,8 +28,15 @@ def _words(rng, *shape):
     return rng.integers(0, P, size=shape, dtype=np.uint64)
 
 
-def _pairs(rng, k):
-    return [(int(a), int(b)) for a, b in _words(rng, k, 2)]
+def _any_words(rng, *shape):
+    """uniform 64-bit words; only one in 2^32 of those is >= p, so one word in eight is then moved into [p, 2^64)"""
+    w = rng.integers(0, 1 << 64, size=shape, dtype=np.uint64)
+    high = rng.integers(P, 1 << 64, size=shape, dtype=np.uint64)
+    return np.where(rng.random(shape) < 0.125, high, w)
+
+
+def _pairs(rng, k, words=_words):
+    return [(int(a), int(b)) for a, b in words(rng, k, 2)]
 
 
 # ---------------------------------------------------------------- the CTL Zs
@@ -121,28 +128,33 @@ def _padded(ctx, cols, stride):
     return DeviceBuffer.from_host(ctx, host)
 
 
-def _check_ctl_quotient(gpu, system, desc, table, degree_bits, rate_bits, num_challenges, seed):
-    """uniform words in place of the two LDEs (neither side needs low degree), random challenges"""
+def _check_ctl_quotient(gpu, system, desc, table, degree_bits, rate_bits, num_challenges, seed, words=_words, nt=None):
+    """uniform words in place of the two LDEs (neither side needs low degree), random challenges; `words` draws them all (_words:
+    below p; _any_words: any u64 — the reference then gets them reduced); `nt`: a handle of `desc` to use instead of a new one"""
     import plonky2_gpu_amd as pg
     from oracle import accel
 
     rng = np.random.default_rng(seed)
     stark = system.tables[table]
     n_ext = 1 << (degree_bits + rate_bits)
-    trace, zs = _words(rng, stark.num_columns, n_ext), _words(rng, desc.num_zs(table), n_ext)
-    sets = [_pairs(rng, num_challenges) for _ in range(sr.quotient_degree_factor(stark))] if stark.pairs else None
-    ctl_challenges, alphas = _pairs(rng, num_challenges), [int(x) for x in _words(rng, num_challenges)]
+    trace, zs = words(rng, stark.num_columns, n_ext), words(rng, desc.num_zs(table), n_ext)
+    sets = [_pairs(rng, num_challenges, words) for _ in range(sr.quotient_degree_factor(stark))] if stark.pairs else None
+    ctl_challenges, alphas = _pairs(rng, num_challenges, words), [int(x) for x in words(rng, num_challenges)]
+    reduced = lambda a: (a % np.uint64(P)).T.tolist()  # noqa: E731
+    mod = lambda pairs: [(a % P, b % P) for a, b in pairs]  # noqa: E731
     with accel.c_backend():
-        exp = np.array(cr.compute_quotient_polys(system, table, num_challenges, degree_bits, rate_bits, trace.T.tolist(), zs.T.tolist(), sets,
-                                                 ctl_challenges, alphas), dtype=np.uint64)
-    nt = pg.NativeStarkTables(gpu, desc)
+        exp = np.array(cr.compute_quotient_polys(system, table, num_challenges, degree_bits, rate_bits, reduced(trace), reduced(zs),
+                                                 sets and [mod(s) for s in sets], mod(ctl_challenges), [a % P for a in alphas]), dtype=np.uint64)
+    own = nt is None
+    nt = pg.NativeStarkTables(gpu, desc) if own else nt
     try:
         for stride in (n_ext, n_ext + 2):
             got = nt.quotient_polys(table, _padded(gpu, trace, stride), _padded(gpu, zs, stride), stride, alphas, sets, ctl_challenges)
             bad = np.argwhere(got != exp)
-            assert bad.size == 0, ("column pitch", stride, "first (challenge, coefficient) that differs", bad[0].tolist(), len(bad))
+            assert bad.size == 0, ("table", table, "column pitch", stride, "first (challenge, coefficient) that differs", bad[0].tolist(), len(bad))
     finally:
-        nt.close()
+        if own:
+            nt.close()
 
 
 @pytest.mark.gpu
