@@ -437,7 +437,8 @@ GlError gl_commit_from_coeffs(const uint64_t *d_coeffs, uint64_t poly_num, uint3
                               uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
                               uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
 /* PolynomialBatch::from_values (oracle.rs:709-731): d_values is transformed IN PLACE into the
- * coefficients (= PolynomialBatch.polynomials), then as gl_commit_from_coeffs. */
+ * coefficients (= PolynomialBatch.polynomials), then as gl_commit_from_coeffs. The arguments are checked before the transform:
+ * a call refused with GL_E_INVALID leaves d_values as it was (with either hasher of gl_commit_from_values_h). */
 GlError gl_commit_from_values(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint32_t rate_bits,
                               uint32_t cap_height, uint32_t salt_size, uint64_t shift, uint64_t *d_lde,
                               uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, void *ctx);
@@ -843,7 +844,7 @@ const char *cudaGetErrorString(int code);
 /* Test hook: element-wise field op on device arrays (op: 0 add, 1 sub, 2 mul, 3 neg, 4 x^7,
  * 5 a + b*b, 6 a * 2^(b mod 192), 7 a + canon(b), 8-16 internal variants, 17 a + (b mod 2^63) * 2^32, 18-27 the grouped
  * forms with deferred corrections); output canonical. d_b may be NULL for unary ops. Ops 100-109: the register-level radix
- * routines of the NTT passes on vectors of sixteen elements (n = 16 x vectors; d_b unused), see csrc/capi.hip. */
+ * routines of the NTT passes on vectors of sixteen elements (n = 16 x vectors; d_b unused), see csrc/probes.hip. */
 GlError gl_debug_field_op(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, uint64_t n, void *ctx);
 /* Measurement hook: a plain streaming copy kernel (16 B per lane, asynchronous on ctx->stream) — the bandwidth a
  * kernel can actually reach on this device, which bench.py reports next to the 8 TB/s specification. */

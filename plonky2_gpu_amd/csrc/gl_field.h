@@ -804,5 +804,11 @@ inline uint64_t pow(uint64_t b, uint64_t e) {
 inline uint64_t inv(uint64_t a) { return pow(a, P - 2); }
 // Field::primitive_root_of_unity (field/src/types.rs:268-272)
 inline uint64_t root_of_unity(unsigned n_log) { return pow(1753635133440165772ULL, 1ULL << (32 - n_log)); }
+// the smallest l with 2^l >= x (util/src/lib.rs log2_ceil); 64 for x > 2^63
+inline uint32_t log2_ceil(uint64_t x) {
+    uint32_t l = 0;
+    while (l < 64 && (1ull << l) < x) l++;
+    return l;
+}
 }  // namespace glh
 #endif  // GL_JIT

@@ -685,9 +685,8 @@ hipError_t tree_layers(uint64_t *digests, uint64_t *cap, uint64_t n_leaves, uint
 }  // namespace
 
 static int log2_exact(uint64_t n) {
-    int l = 0;
-    while ((1ull << l) < n) l++;
-    return (1ull << l) == n ? l : -1;
+    const uint32_t l = glh::log2_ceil(n);
+    return l < 64 && (1ull << l) == n ? (int)l : -1;
 }
 
 hipError_t merkle_tree_from_columns(const uint64_t *cols, uint32_t leaf_len, uint64_t n_leaves, uint64_t col_stride,
@@ -767,9 +766,7 @@ hipError_t merkle_open_batch(const uint64_t *leaves, uint64_t row_stride, uint64
                              uint32_t cap_height, const uint64_t *digests, const uint64_t *d_idx, uint32_t count, uint64_t *out_leaves,
                              uint64_t *out_sib, hipStream_t stream, uint64_t idx_mask, uint32_t idx_shift) {
     if (count == 0) return hipSuccess;
-    uint32_t lg = 0;
-    while ((1ull << lg) < n_leaves) lg++;
-    const uint32_t num_layers = lg - cap_height;
+    const uint32_t num_layers = glh::log2_ceil(n_leaves) - cap_height;
     const uint64_t subtree_digests = 2 * ((n_leaves >> cap_height) - 1);
     hipLaunchKernelGGL(merkle_open_kernel, dim3(count), dim3(64), 0, stream, leaves, row_stride, elem_stride, leaf_len, digests, num_layers,
                        subtree_digests, d_idx, idx_mask, idx_shift, out_leaves, out_sib);

@@ -14,7 +14,7 @@ struct NttTables {
     uint64_t *twh = nullptr;
     // Workspace for natural-order multi-pass transforms (the last pass writes transposed, so the
     // intermediate cannot live in the caller's buffer), 512 MiB = 64 columns of 2^20: one launch pair
-    // per batch. One per CONTEXT (capi.hip CtxState holds a copy of the device's tables with its own
+    // per batch. One per CONTEXT (ctx.h CtxState holds a copy of the device's tables with its own
     // scratch), so that two contexts on one device never meet in it.
     uint64_t *scratch = nullptr;
     uint64_t scratch_elems = 0;

@@ -1162,7 +1162,7 @@ hipError_t ntt_tables_create(NttTables *tb) {
     tb->twh = tb->twl + 4096;
     e = hipMemcpy(tb->twl, h, 2 * 4096 * sizeof(uint64_t), hipMemcpyHostToDevice);
     free(h);
-    // the workspace (`scratch`) belongs to a context, not to the device: capi.hip CtxState
+    // the workspace (`scratch`) belongs to a context, not to the device: ctx.h CtxState
     return e;
 }
 

@@ -361,8 +361,7 @@ __global__ __launch_bounds__(128) void quotient_values_fast_kernel(const Quotien
 hipError_t quotient_values(const NttTables &tb, const QuotientArgs &a, uint64_t *out, hipStream_t stream) {
     if (a.num_challenges == 0 || a.num_challenges > MAX_CHALLENGES || a.quotient_degree_factor < 2 || a.num_routed == 0)
         return hipErrorInvalidValue;
-    uint32_t qdb = 0;
-    while ((1u << qdb) < a.quotient_degree_factor) qdb++;  // log2_ceil
+    const uint32_t qdb = glh::log2_ceil(a.quotient_degree_factor);
     if (qdb > a.rate_bits || a.degree_bits + qdb > 24) return hipErrorInvalidValue;
     const uint32_t num_prods = num_partial_products(a.num_routed, a.quotient_degree_factor);
     if (a.num_challenges * (2 + num_prods) > MAX_TERMS) return hipErrorInvalidValue;

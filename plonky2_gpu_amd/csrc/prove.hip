@@ -19,22 +19,16 @@
 #include <vector>
 
 #include "../../include/plonky2_hip.h"
+#include "commit.h"
 #include "gate_jit.h"
 #include "gl_field.h"
 #include "stark.h"
 
+using namespace plonky2_hip;
+
 namespace {
 
 using glh::P;
-
-#define TRY(expr)                  \
-    do {                           \
-        GlError _e = (expr);       \
-        if (_e.code != 0) return _e; \
-    } while (0)
-
-GlError ok() { return GlError{0, nullptr}; }
-GlError fail(const std::string &m) { return GlError{GL_E_INVALID, strdup(m.c_str())}; }
 
 struct E2 {  // a + bX, X^2 = 7 (field/src/goldilocks_extensions.rs:13-26)
     uint64_t a, b;
@@ -235,18 +229,6 @@ uint32_t num_partial_products(uint32_t routed, uint32_t qdf) { return (routed + 
 
 constexpr uint32_t SALT_SIZE = 4;  // fri/oracle.rs:41
 
-__global__ void canon_copy_kernel(uint64_t *dst, const uint64_t *src, uint64_t n) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) dst[i] = gl::canon(src[i]);
-}
-GlError canon_copy(uint64_t *d_dst, const uint64_t *d_src, uint64_t n, void *ctx) {
-    if (n == 0) return ok();
-    const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(canon_copy_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, *reinterpret_cast<hipStream_t *>(ctx), d_dst, d_src, n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return ok();
-}
-
 // d_salt: SALT_SIZE columns of n_ext caller-provided random elements in leaf order (a blinded commitment, prover.rs:84, 125, 174), or null
 GlError commit(Batch *b, DevBuf &&polys, bool from_values, uint32_t n_polys, const ProverShape &c, void *ctx, const uint64_t *d_salt = nullptr,
               bool fetch_cap = true) {
@@ -261,7 +243,9 @@ GlError commit(Batch *b, DevBuf &&polys, bool from_values, uint32_t n_polys, con
     // the salt columns sit behind the LDE's columns and are hashed with them (gl_commit_from_* reads them as given). They also go into
     // the proof verbatim (fri/prover.rs:203-210), where every word must be canonical like the reference's F::rand_vec output
     // (fri/oracle.rs:998-1002): a caller who fills d_salts with raw 64-bit randoms gets them reduced here, not >= p words on the wire.
-    if (salt) TRY(canon_copy(b->lde.p + (uint64_t)n_polys * n_ext, d_salt, (uint64_t)salt * n_ext, ctx));
+    if (salt)
+        if (hipError_t e = canon_copy(b->lde.p + (uint64_t)n_polys * n_ext, d_salt, (uint64_t)salt * n_ext, ctx_stream(ctx)); e != hipSuccess)
+            return fail(GL_E_INVALID, hipGetErrorString(e));
     if (from_values)
         TRY(gl_commit_from_values_h(c.hasher, b->coeffs.p, n_polys, c.degree_bits, c.rate_bits, c.cap_height, salt, 7, b->lde.p, nullptr, b->digests.p,
                                     b->cap_d.p, ctx));
@@ -316,13 +300,13 @@ struct Stages {
 // Asynchronous copies between device memory and the pool's page-locked staging, on the context's first stream.
 GlError copy_async(void *dst, const void *src, uint64_t bytes, bool to_host, void *ctx) {
     if (!bytes) return ok();
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, *reinterpret_cast<hipStream_t *>(ctx));
-    if (e != hipSuccess) return fail(std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, ctx_stream(ctx));
+    if (e != hipSuccess) return fail(GL_E_INVALID, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
     return ok();
 }
 GlError stream_sync(void *ctx) {
-    const hipError_t e = hipStreamSynchronize(*reinterpret_cast<hipStream_t *>(ctx));
-    if (e != hipSuccess) return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    const hipError_t e = hipStreamSynchronize(ctx_stream(ctx));
+    if (e != hipSuccess) return fail(GL_E_INVALID, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     return ok();
 }
 
@@ -368,10 +352,8 @@ GlError fri_shapes(const ProverShape &c, FriLayout *L) {
     for (uint32_t li = 0; li < L->n_fri; li++) {
         const uint32_t ab = c.arity_bits[li];
         L->fs[li].n_leaves = (len << c.rate_bits) >> ab, L->fs[li].leaf_len = 2u << ab;
-        if (L->fs[li].n_leaves < (1ull << c.cap_height)) return fail("FRI layer smaller than the Merkle cap");
-        uint32_t lg = 0;
-        while ((1ull << lg) < L->fs[li].n_leaves) lg++;
-        L->fs[li].layers = lg - c.cap_height;
+        if (L->fs[li].n_leaves < (1ull << c.cap_height)) return fail(GL_E_INVALID, "FRI layer smaller than the Merkle cap");
+        L->fs[li].layers = glh::log2_ceil(L->fs[li].n_leaves) - c.cap_height;
         shift += ab;
         L->fs[li].shift = shift;
         len >>= ab;
@@ -436,8 +418,7 @@ GlError fri_prove(const ProverShape &c, const FriLayout &L, uint64_t *D, uint64_
         DevBuf coeffs = std::move(final_poly), vals;
         uint64_t len = n, shift = 7;
         auto lde = [&](DevBuf *dst) -> GlError {
-            uint32_t lg = 0;
-            while ((1ull << lg) < len) lg++;
+            const uint32_t lg = glh::log2_ceil(len);
             TRY(dst->alloc(2 * (len << c.rate_bits)));
             return gl_coset_lde_batch(coeffs.p, dst->p, 2, lg, c.rate_bits, shift, len, len << c.rate_bits, ctx);
         };
@@ -484,8 +465,8 @@ GlError fri_prove(const ProverShape &c, const FriLayout &L, uint64_t *D, uint64_
 }
 
 GlError fri_check_pow(const ProverShape &c, const FriLayout &L, const uint64_t *H, uint64_t pow_witness) {
-    if (c.pow_bits && (H[L.resp_idx.off] >> (64 - c.pow_bits)) != 0) return fail("proof-of-work response does not have the required leading zeros");
-    if (H[L.pow_w.off] != pow_witness) return fail("proof-of-work witness changed between the search and the transcript");
+    if (c.pow_bits && (H[L.resp_idx.off] >> (64 - c.pow_bits)) != 0) return fail(GL_E_INVALID, "proof-of-work response does not have the required leading zeros");
+    if (H[L.pow_w.off] != pow_witness) return fail(GL_E_INVALID, "proof-of-work witness changed between the search and the transcript");
     return ok();
 }
 
@@ -510,7 +491,7 @@ void fri_write(Bytes &out, const ProverShape &c, const FriLayout &L, const uint6
 
 GlError bytes_out(const Bytes &out, uint8_t **proof, uint64_t *proof_len) {
     uint8_t *buf = static_cast<uint8_t *>(malloc(out.v.size() ? out.v.size() : 1));
-    if (!buf) return fail("out of memory");
+    if (!buf) return fail(GL_E_INVALID, "out of memory");
     memcpy(buf, out.v.data(), out.v.size());
     *proof = buf;
     *proof_len = out.v.size();
@@ -523,12 +504,12 @@ extern "C" {
 
 static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **circuit, void *ctx) {
     if (!d || !circuit || !ctx || !d->h_k_is || !d->h_constants || !d->h_sigmas || (d->fri.num_reductions && !d->fri.reduction_arity_bits))
-        return fail("null pointer");
+        return fail(GL_E_INVALID, "null pointer");
     if (d->struct_size != sizeof(GlCircuitDesc))
-        return fail("GlCircuitDesc.struct_size does not equal sizeof(GlCircuitDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+        return fail(GL_E_INVALID, "GlCircuitDesc.struct_size does not equal sizeof(GlCircuitDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
     if (d->degree_bits > 24 || d->num_challenges == 0 || d->num_challenges > 4 || d->num_routed_wires > d->num_wires ||
         d->quotient_degree_factor < 2 || d->quotient_degree_factor >= d->num_routed_wires)
-        return fail("bad circuit shape (the prover needs quotient_degree_factor < num_routed_wires, prover.rs:99-102)");
+        return fail(GL_E_INVALID, "bad circuit shape (the prover needs quotient_degree_factor < num_routed_wires, prover.rs:99-102)");
     if (hasher == GL_HASHER_KECCAK25) {
         // KeccakHash<25>::hash_or_noop panics on a leaf of exactly four elements (a 32-byte slice of a 25-byte vector, plonk/config.rs:
         // 56-63): refuse such a circuit here, before anything is allocated, not in the middle of a proof
@@ -542,11 +523,11 @@ static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **ci
                             {"quotient", nch * qdf + salt}};
         for (const auto &cm : commitments)
             if (cm.leaf_len == 4)
-                return fail(std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
+                return fail(GL_E_INVALID, std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
                             " commitment have 4");
         for (uint32_t li = 0; li < d->fri.num_reductions; li++)
             if (d->fri.reduction_arity_bits[li] == 1)
-                return fail("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
+                return fail(GL_E_INVALID, "KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
                             " has arity_bits = 1: its leaves are 2 extension elements");
     }
     Circuit *c = new Circuit();
@@ -597,7 +578,7 @@ static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **ci
         CTRY(hash_no_pad(parts.data(), parts.size(), c->digest, ctx));
     }
     if (d->num_gates) {
-        if (!d->h_instrs || !d->h_gates) return bail(fail("null gate program"));
+        if (!d->h_instrs || !d->h_gates) return bail(fail(GL_E_INVALID, "null gate program"));
         c->num_gates = d->num_gates, c->num_selectors = d->num_selectors;
         {
             std::string verr;
@@ -605,9 +586,9 @@ static GlError circuit_create(uint32_t hasher, const GlCircuitDesc *d, void **ci
             if (!plonky2_hip::gate_programs_validate(reinterpret_cast<const uint16_t *>(d->h_instrs), d->num_instrs, reinterpret_cast<const uint32_t *>(d->h_gates),
                                         d->num_gates, d->num_immediates, d->num_selectors, d->num_gate_constraints, &wires_needed,
                                         &constants_needed, &verr))
-                return bail(fail("gate programs: " + verr));
+                return bail(fail(GL_E_INVALID, "gate programs: " + verr));
             if (wires_needed > c->num_wires || constants_needed > c->num_constants)
-                return bail(fail("gate programs load wire " + std::to_string(wires_needed ? wires_needed - 1 : 0) + " / constant column " +
+                return bail(fail(GL_E_INVALID, "gate programs load wire " + std::to_string(wires_needed ? wires_needed - 1 : 0) + " / constant column " +
                                  std::to_string(constants_needed ? constants_needed - 1 : 0) + " but the circuit has " + std::to_string(c->num_wires) +
                                  " wires and " + std::to_string(c->num_constants) + " constants"));
         }
@@ -635,19 +616,19 @@ GlError gl_circuit_create(const GlCircuitDesc *d, void **circuit, void *ctx) { r
 
 GlError gl_circuit_create_h(uint32_t hasher, const GlCircuitDesc *d, void **circuit, void *ctx) {
     if (hasher == GL_HASHER_POSEIDON) return gl_circuit_create(d, circuit, ctx);
-    if (hasher != GL_HASHER_KECCAK25) return fail("unknown hasher");
+    if (hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
     return circuit_create(hasher, d, circuit, ctx);
 }
 
 void gl_circuit_destroy(void *circuit) { delete static_cast<Circuit *>(circuit); }
 
 GlError gl_circuit_trim(void *circuit) {
-    if (!circuit) return fail("null pointer");
+    if (!circuit) return fail(GL_E_INVALID, "null pointer");
     return static_cast<Circuit *>(circuit)->trim();
 }
 
 GlError gl_circuit_info(const void *circuit, uint64_t h_digest[4], uint64_t *h_constants_sigmas_cap) {
-    if (!circuit) return fail("null pointer");
+    if (!circuit) return fail(GL_E_INVALID, "null pointer");
     const Circuit *c = static_cast<const Circuit *>(circuit);
     if (h_digest) memcpy(h_digest, c->digest, 32);
     if (h_constants_sigmas_cap) memcpy(h_constants_sigmas_cap, c->cs.cap.data(), c->cs.cap.size() * 8);
@@ -664,10 +645,10 @@ void gl_bytes_free(uint8_t *p) { free(p); }
 // an upload, a launch, a download and a synchronisation) and one per cap, opening batch and query batch.
 static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const uint64_t *h_public_inputs, uint32_t num_public_inputs,
                           const uint64_t *d_salts, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms, void *ctx) {
-    if (!circuit || !d_wires || !proof || !proof_len || !ctx || (num_public_inputs && !h_public_inputs)) return fail("null pointer");
+    if (!circuit || !d_wires || !proof || !proof_len || !ctx || (num_public_inputs && !h_public_inputs)) return fail(GL_E_INVALID, "null pointer");
     const Circuit &c = *static_cast<const Circuit *>(circuit);
-    if (c.hiding && !d_salts) return fail("the circuit's FRI parameters are hiding (zero_knowledge): prove it with gl_prove_zk and salt columns");
-    if (!c.hiding && d_salts) return fail("gl_prove_zk on a circuit whose FRI parameters are not hiding");
+    if (c.hiding && !d_salts) return fail(GL_E_INVALID, "the circuit's FRI parameters are hiding (zero_knowledge): prove it with gl_prove_zk and salt columns");
+    if (!c.hiding && d_salts) return fail(GL_E_INVALID, "gl_prove_zk on a circuit whose FRI parameters are not hiding");
     Pool *pool = c.pool_of(ctx);
     PoolScope pool_scope(pool);  // every DevBuf below comes from / returns to the circuit's pool of this context
     const uint32_t db = c.degree_bits, nch = c.num_challenges, qdf = c.qdf, npi = num_public_inputs;
@@ -741,8 +722,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     TRY(stream_sync(ctx));
     alphas.assign(H + alphas_s.off, H + alphas_s.off + nch);
     // quotient polynomials (prover.rs:137-151)
-    uint32_t qdb = 0;
-    while ((1u << qdb) < qdf) qdb++;
+    const uint32_t qdb = glh::log2_ceil(qdf);
     DevBuf quotient, work;
     TRY(quotient.alloc((uint64_t)nch << (db + qdb)));
     {
@@ -785,7 +765,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
             for (uint32_t k = 0; k < nch; k++) {
                 TRY(gl_memcpy_d2h(tail.data(), quotient.p + ((uint64_t)k << (db + qdb)) + (uint64_t)qdf * n, tail.size() * 8, ctx));
                 for (uint64_t t : tail)
-                    if (t) return fail("Quotient has failed, the vanishing polynomial is not divisible by Z_H");
+                    if (t) return fail(GL_E_INVALID, "Quotient has failed, the vanishing polynomial is not divisible by Z_H");
                 TRY(gl_memcpy_d2d(chunks.p + (uint64_t)k * qdf * n, quotient.p + ((uint64_t)k << (db + qdb)), 8ull * qdf * n, ctx));
             }
         }
@@ -796,7 +776,7 @@ static GlError prove_impl(const void *circuit, const uint64_t *d_wires, const ui
     TRY(fetch(zeta_s));
     TRY(stream_sync(ctx));
     const E2 zeta{H[zeta_s.off], H[zeta_s.off + 1]};
-    if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail("Opening point is in the subgroup.");
+    if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail(GL_E_INVALID, "Opening point is in the subgroup.");
     const uint64_t g = glh::root_of_unity(db);
     const E2 g_zeta = e2_mul(E2{g, 0}, zeta);
     // OpeningSet::new (plonk/proof.rs:305-334): every oracle's polynomials at zeta, the Zs also at g * zeta, left in device memory
@@ -860,12 +840,12 @@ GlError gl_prove(const void *circuit, const uint64_t *d_wires, const uint64_t *h
 // pool per context; the launches of its gate kernel take turns) and run at the same time: each fills the other's latency-bound phases.
 GlError gl_prove_many(const void *circuit, const uint64_t *const *d_wires, const uint64_t *const *h_public_inputs, uint32_t num_public_inputs,
                       uint32_t count, uint8_t **proofs, uint64_t *proof_lens, void *const *ctxs, uint32_t in_flight) {
-    if (!circuit || !proofs || !proof_lens || !ctxs || (count && (!d_wires || (num_public_inputs && !h_public_inputs)))) return fail("null pointer");
-    if (in_flight == 0 || in_flight > 16) return fail("in_flight must be 1..16");
+    if (!circuit || !proofs || !proof_lens || !ctxs || (count && (!d_wires || (num_public_inputs && !h_public_inputs)))) return fail(GL_E_INVALID, "null pointer");
+    if (in_flight == 0 || in_flight > 16) return fail(GL_E_INVALID, "in_flight must be 1..16");
     for (uint32_t w = 0; w < in_flight; w++) {
-        if (!ctxs[w]) return fail("null context");
+        if (!ctxs[w]) return fail(GL_E_INVALID, "null context");
         for (uint32_t v = 0; v < w; v++)
-            if (ctxs[v] == ctxs[w]) return fail("every worker needs a context of its own");
+            if (ctxs[v] == ctxs[w]) return fail(GL_E_INVALID, "every worker needs a context of its own");
     }
     for (uint32_t i = 0; i < count; i++) proofs[i] = nullptr, proof_lens[i] = 0;
     std::vector<GlError> errs(in_flight, GlError{0, nullptr});
@@ -899,7 +879,7 @@ GlError gl_prove_many(const void *circuit, const uint64_t *const *d_wires, const
 
 GlError gl_prove_zk(const void *circuit, const uint64_t *d_wires, const uint64_t *h_public_inputs, uint32_t num_public_inputs,
                     const uint64_t *d_salts, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms, void *ctx) {
-    if (!d_salts) return fail("gl_prove_zk: null salt columns");
+    if (!d_salts) return fail(GL_E_INVALID, "gl_prove_zk: null salt columns");
     return prove_impl(circuit, d_wires, h_public_inputs, num_public_inputs, d_salts, proof, proof_len, h_stage_ms, ctx);
 }
 
@@ -920,22 +900,25 @@ struct Stark : ProverShape {
     }
 };
 
-GlError hip_fail(hipError_t e, const char *what) { return GlError{(int)e, strdup((std::string(what) + ": " + hipGetErrorString(e)).c_str())}; }
+GlError tables_of(void *ctx, const NttTables **tb) {
+    if (hipError_t e = ctx_tables(ctx, tb); e != hipSuccess) return hip_fail(e, "context tables");
+    return ok();
+}
 
 // the quotient values of one trace, then their coset_ifft (prover.rs:314-318); ctl / h_ctl_challenges: the table's CTL checks, or null
 GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride, const uint64_t *h_alphas,
                        const uint64_t *h_challenges, const uint64_t *d_public_inputs, uint64_t *d_out, void *ctx,
                        const plonky2_hip::StarkCtlDev *ctl = nullptr, const uint64_t *h_ctl_challenges = nullptr) {
     const plonky2_hip::NttTables *tb;
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     plonky2_hip::StarkQuotientArgs a = {};
     a.instrs = reinterpret_cast<const uint16_t *>(s.d_instrs.p), a.num_instrs = s.num_instrs, a.imms = s.d_imms.p, a.public_inputs = d_public_inputs;
     a.trace_lde = d_trace_lde, a.zs_lde = d_zs_lde, a.column_stride = column_stride, a.pairs = s.pairs();
     a.alphas = h_alphas, a.challenges = h_challenges;
     a.num_challenges = s.num_challenges, a.qdf = s.qdf, a.degree_bits = s.degree_bits, a.rate_bits = s.rate_bits;
     if (ctl) a.ctl = *ctl, a.ctl_challenges = h_ctl_challenges;
-    const hipError_t e = plonky2_hip::stark_quotient_values(*tb, a, d_out, *reinterpret_cast<hipStream_t *>(ctx));
-    if (e == hipErrorInvalidValue) return fail("inconsistent arguments of the STARK quotient (column_stride / challenges / sizes)");
+    const hipError_t e = plonky2_hip::stark_quotient_values(*tb, a, d_out, ctx_stream(ctx));
+    if (e == hipErrorInvalidValue) return fail(GL_E_INVALID, "inconsistent arguments of the STARK quotient (column_stride / challenges / sizes)");
     if (e != hipSuccess) return hip_fail(e, "stark_quotient_values");
     const uint32_t log_size = s.degree_bits + s.qdb;
     return gl_coset_ntt_batch(d_out, s.num_challenges, log_size, 1ull << log_size, 7, 1, ctx);
@@ -946,36 +929,35 @@ GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64
 GlError stark_check(uint32_t hasher, const GlStarkDesc *d, uint32_t num_ctl_zs) {
     if (!d || !d->h_instrs || (d->num_immediates && !d->h_immediates) || (d->fri.num_reductions && !d->fri.reduction_arity_bits) ||
         (d->num_pairs && (!d->h_column_pairs || !d->h_pair_bounds)))
-        return fail("null pointer");
+        return fail(GL_E_INVALID, "null pointer");
     if (d->struct_size != sizeof(GlStarkDesc))
-        return fail("GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
-    if (hasher != GL_HASHER_POSEIDON && hasher != GL_HASHER_KECCAK25) return fail("unknown hasher");
-    if (d->fri.hiding) return fail("a STARK's FRI parameters are not hiding (starky: fri_params(degree_bits, false))");
+        return fail(GL_E_INVALID, "GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+    if (hasher != GL_HASHER_POSEIDON && hasher != GL_HASHER_KECCAK25) return fail(GL_E_INVALID, "unknown hasher");
+    if (d->fri.hiding) return fail(GL_E_INVALID, "a STARK's FRI parameters are not hiding (starky: fri_params(degree_bits, false))");
     if (d->degree_bits == 0 || d->degree_bits + d->fri.rate_bits > 24 || d->num_columns == 0 || d->num_columns > 65535 || d->num_public_inputs > 65535 ||
         d->num_challenges == 0 || d->num_challenges > plonky2_hip::STARK_MAX_CHALLENGES || d->constraint_degree == 0)
-        return fail("bad STARK shape (1 <= degree_bits, degree_bits + rate_bits <= 24, 1 <= num_columns, 1 <= num_challenges <= 4, 1 <= constraint_degree)");
+        return fail(GL_E_INVALID, "bad STARK shape (1 <= degree_bits, degree_bits + rate_bits <= 24, 1 <= num_columns, 1 <= num_challenges <= 4, 1 <= constraint_degree)");
     const uint32_t qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;  // stark.rs:79-81
-    uint32_t qdb = 0;
-    while ((1u << qdb) < qdf) qdb++;
-    if (qdf > plonky2_hip::STARK_MAX_QDF) return fail("quotient_degree_factor > 16");
-    if (qdb > d->fri.rate_bits) return fail("Having constraints of degree higher than the rate is not supported yet. (log2_ceil(quotient_degree_factor) > rate_bits, prover.rs:223-226)");
+    const uint32_t qdb = glh::log2_ceil(qdf);
+    if (qdf > plonky2_hip::STARK_MAX_QDF) return fail(GL_E_INVALID, "quotient_degree_factor > 16");
+    if (qdb > d->fri.rate_bits) return fail(GL_E_INVALID, "Having constraints of degree higher than the rate is not supported yet. (log2_ceil(quotient_degree_factor) > rate_bits, prover.rs:223-226)");
     uint32_t total_arity = 0;
     for (uint32_t li = 0; li < d->fri.num_reductions; li++) total_arity += d->fri.reduction_arity_bits[li];
     if (d->fri.cap_height > d->degree_bits + d->fri.rate_bits || total_arity > d->degree_bits + d->fri.rate_bits - d->fri.cap_height || total_arity > d->degree_bits)
-        return fail("FRI total reduction arity is too large.");
+        return fail(GL_E_INVALID, "FRI total reduction arity is too large.");
     if (d->num_pairs) {
-        if (d->h_pair_bounds[0] != 0) return fail("h_pair_bounds must start at 0");
+        if (d->h_pair_bounds[0] != 0) return fail(GL_E_INVALID, "h_pair_bounds must start at 0");
         for (uint32_t p = 0; p < d->num_pairs; p++)
-            if (d->h_pair_bounds[p + 1] < d->h_pair_bounds[p]) return fail("h_pair_bounds must not decrease");
+            if (d->h_pair_bounds[p + 1] < d->h_pair_bounds[p]) return fail(GL_E_INVALID, "h_pair_bounds must not decrease");
         for (uint32_t k = 0; k < 2 * d->h_pair_bounds[d->num_pairs]; k++)
-            if (d->h_column_pairs[k] >= d->num_columns) return fail("permutation pair: column out of range");
+            if (d->h_column_pairs[k] >= d->num_columns) return fail(GL_E_INVALID, "permutation pair: column out of range");
     }
     const uint32_t num_zs = d->num_pairs ? plonky2_hip::stark_num_zs(d->num_pairs, d->num_challenges, qdf) : 0;
     {
         std::string verr;
         if (!plonky2_hip::stark_program_validate(reinterpret_cast<const uint16_t *>(d->h_instrs), d->num_instrs, d->h_immediates, d->num_immediates,
                                                  d->num_columns, d->num_public_inputs, &verr))
-            return fail(verr);
+            return fail(GL_E_INVALID, verr);
     }
     if (hasher == GL_HASHER_KECCAK25) {  // as gl_circuit_create_h: KeccakHash<25>::hash_or_noop panics on a leaf of exactly four elements
         const struct {
@@ -984,11 +966,11 @@ GlError stark_check(uint32_t hasher, const GlStarkDesc *d, uint32_t num_ctl_zs) 
         } commitments[3] = {{"trace", d->num_columns}, {num_ctl_zs ? "permutation / CTL Zs" : "permutation Zs", num_zs + num_ctl_zs}, {"quotient", d->num_challenges * qdf}};
         for (const auto &cm : commitments)
             if (cm.leaf_len == 4)
-                return fail(std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
+                return fail(GL_E_INVALID, std::string("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and the leaves of the ") + cm.name +
                             " commitment have 4");
         for (uint32_t li = 0; li < d->fri.num_reductions; li++)
             if (d->fri.reduction_arity_bits[li] == 1)
-                return fail("KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
+                return fail(GL_E_INVALID, "KeccakHash<25> cannot hash a Merkle leaf of 4 elements (plonk/config.rs:56-63) and FRI reduction " + std::to_string(li) +
                             " has arity_bits = 1: its leaves are 2 extension elements");
     }
     return ok();
@@ -997,11 +979,10 @@ GlError stark_check(uint32_t hasher, const GlStarkDesc *d, uint32_t num_ctl_zs) 
 // after stark_check
 GlError stark_build(uint32_t hasher, const GlStarkDesc *d, Stark **stark, void *ctx) {
     const uint32_t qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;
-    uint32_t qdb = 0;
-    while ((1u << qdb) < qdf) qdb++;
+    const uint32_t qdb = glh::log2_ceil(qdf);
     const uint32_t num_column_pairs = d->num_pairs ? d->h_pair_bounds[d->num_pairs] : 0;
     const plonky2_hip::NttTables *tb;  // makes the context's device current before the first allocation
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     Stark *s = new Stark();
     s->hasher = hasher;
     s->degree_bits = d->degree_bits, s->num_columns = d->num_columns, s->num_public_inputs = d->num_public_inputs;
@@ -1125,7 +1106,7 @@ GlError stark_prove_one(const Stark &c, const uint64_t *d_trace, const uint64_t 
     // On its own: a fresh Challenger observes the trace cap (prover.rs:72-74), nothing else. As a table: the shared Challenger has
     // observed every trace cap already and is compacted (evm/src/prover.rs:271).
     const uint32_t begin = ctl ? GL_CHALLENGER_COMPACT : GL_CHALLENGER_RESET;
-    auto filter_check = [&]() { return ctl && *ctl->h_filter_flag ? fail("Non-binary filter?") : ok(); };
+    auto filter_check = [&]() { return ctl && *ctl->h_filter_flag ? fail(GL_E_INVALID, "Non-binary filter?") : ok(); };
     Batch zs;
     std::vector<uint64_t> perm_challenges;
     if (has_zs) {
@@ -1175,7 +1156,7 @@ GlError stark_prove_one(const Stark &c, const uint64_t *d_trace, const uint64_t 
             for (uint32_t k = 0; k < nch; k++) {
                 TRY(gl_memcpy_d2h(tail.data(), quotient.p + ((uint64_t)k << (db + qdb)) + (uint64_t)qdf * n, tail.size() * 8, ctx));
                 for (uint64_t t : tail)
-                    if (t) return fail("Quotient has failed, the vanishing polynomial is not divisible by Z_H");
+                    if (t) return fail(GL_E_INVALID, "Quotient has failed, the vanishing polynomial is not divisible by Z_H");
                 TRY(gl_memcpy_d2d(chunks.p + (uint64_t)k * qdf * n, quotient.p + ((uint64_t)k << (db + qdb)), 8ull * qdf * n, ctx));
             }
         }
@@ -1186,7 +1167,7 @@ GlError stark_prove_one(const Stark &c, const uint64_t *d_trace, const uint64_t 
     TRY(fetch(zeta_s));
     TRY(stream_sync(ctx));
     const E2 zeta{H[zeta_s.off], H[zeta_s.off + 1]};
-    if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail("Opening point is in the subgroup.");
+    if (E2 zn = e2_pow(zeta, n); zn.a == 1 && zn.b == 0) return fail(GL_E_INVALID, "Opening point is in the subgroup.");
     const uint64_t g = glh::root_of_unity(db);
     const E2 g_zeta = e2_mul(E2{g, 0}, zeta), g_inv{glh::inv(g), 0};
     // StarkOpeningSet::new (proof.rs:138-159; evm/src/proof.rs:190-224): trace and Zs at zeta and g * zeta, the quotient at zeta, the
@@ -1253,7 +1234,7 @@ GlError stark_prove_one(const Stark &c, const uint64_t *d_trace, const uint64_t 
 extern "C" {
 
 GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, void *ctx) {
-    if (!d || !stark || !ctx) return fail("null pointer");
+    if (!d || !stark || !ctx) return fail(GL_E_INVALID, "null pointer");
     TRY(stark_check(hasher, d, 0));
     Stark *s = nullptr;
     TRY(stark_build(hasher, d, &s, ctx));
@@ -1264,20 +1245,20 @@ GlError gl_stark_create(uint32_t hasher, const GlStarkDesc *d, void **stark, voi
 void gl_stark_destroy(void *stark) { delete static_cast<Stark *>(stark); }
 
 GlError gl_stark_trim(void *stark) {
-    if (!stark) return fail("null pointer");
+    if (!stark) return fail(GL_E_INVALID, "null pointer");
     return static_cast<Stark *>(stark)->trim();
 }
 
 GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_challenges, uint64_t *d_zs,
                                 void *ctx) {
-    if (!stark || !d_trace || !h_challenges || !d_zs || !ctx) return fail("null pointer");
+    if (!stark || !d_trace || !h_challenges || !d_zs || !ctx) return fail(GL_E_INVALID, "null pointer");
     const Stark &s = *static_cast<const Stark *>(stark);
-    if (!s.num_pairs) return fail("the STARK has no permutation pairs");
-    if (trace_stride < (1ull << s.degree_bits)) return fail("trace_stride smaller than the column length");
+    if (!s.num_pairs) return fail(GL_E_INVALID, "the STARK has no permutation pairs");
+    if (trace_stride < (1ull << s.degree_bits)) return fail(GL_E_INVALID, "trace_stride smaller than the column length");
     const plonky2_hip::NttTables *tb;
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     const hipError_t e = plonky2_hip::stark_permutation_zs(*tb, d_trace, trace_stride, s.pairs(), h_challenges, s.num_challenges, s.qdf, s.degree_bits, d_zs,
-                                                           *reinterpret_cast<hipStream_t *>(ctx));
+                                                           ctx_stream(ctx));
     if (e != hipSuccess) return hip_fail(e, "stark_permutation_zs");
     return ok();
 }
@@ -1286,11 +1267,11 @@ GlError gl_stark_permutation_zs(const void *stark, const uint64_t *d_trace, uint
 static GlError quotient_polys_call(const Stark &s, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride, const uint64_t *h_alphas,
                                    const uint64_t *h_challenges, const uint64_t *h_public_inputs, uint64_t *d_quotient_polys, void *ctx,
                                    const plonky2_hip::StarkCtlDev *ctl, const uint64_t *h_ctl_challenges) {
-    if (s.num_pairs && (!d_zs_lde || !h_challenges)) return fail("the STARK has permutation pairs: d_zs_lde and h_challenges are needed");
-    if (s.num_public_inputs && !h_public_inputs) return fail("null public inputs");
-    if (column_stride < (1ull << (s.degree_bits + s.rate_bits))) return fail("column_stride smaller than the LDE's column length n << rate_bits");
+    if (s.num_pairs && (!d_zs_lde || !h_challenges)) return fail(GL_E_INVALID, "the STARK has permutation pairs: d_zs_lde and h_challenges are needed");
+    if (s.num_public_inputs && !h_public_inputs) return fail(GL_E_INVALID, "null public inputs");
+    if (column_stride < (1ull << (s.degree_bits + s.rate_bits))) return fail(GL_E_INVALID, "column_stride smaller than the LDE's column length n << rate_bits");
     const plonky2_hip::NttTables *tb;  // the context's device becomes current
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     DevBuf pis;
     TRY(pis.alloc(s.num_public_inputs));
     std::vector<uint64_t> h_pis(s.num_public_inputs);
@@ -1303,19 +1284,19 @@ static GlError quotient_polys_call(const Stark &s, const uint64_t *d_trace_lde, 
 GlError gl_stark_quotient_polys(const void *stark, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde, uint64_t column_stride,
                                 const uint64_t *h_alphas, const uint64_t *h_challenges, const uint64_t *h_public_inputs,
                                 uint64_t *d_quotient_polys, void *ctx) {
-    if (!stark || !d_trace_lde || !h_alphas || !d_quotient_polys || !ctx) return fail("null pointer");
+    if (!stark || !d_trace_lde || !h_alphas || !d_quotient_polys || !ctx) return fail(GL_E_INVALID, "null pointer");
     return quotient_polys_call(*static_cast<const Stark *>(stark), d_trace_lde, d_zs_lde, column_stride, h_alphas, h_challenges, h_public_inputs,
                                d_quotient_polys, ctx, nullptr, nullptr);
 }
 
 GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_t *h_public_inputs, uint8_t **proof, uint64_t *proof_len,
                        double *h_stage_ms, void *ctx) {
-    if (!stark || !d_trace || !proof || !proof_len || !ctx) return fail("null pointer");
+    if (!stark || !d_trace || !proof || !proof_len || !ctx) return fail(GL_E_INVALID, "null pointer");
     const Stark &c = *static_cast<const Stark *>(stark);
-    if (c.num_public_inputs && !h_public_inputs) return fail("null public inputs");
+    if (c.num_public_inputs && !h_public_inputs) return fail(GL_E_INVALID, "null public inputs");
     {  // the context's device is current from here on, whatever the calling thread had: every allocation below follows it
         const plonky2_hip::NttTables *tb;
-        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+        TRY(tables_of(ctx, &tb));
     }
     if (h_stage_ms) memset(h_stage_ms, 0, sizeof(double) * GL_STARK_STAGES);
     Bytes out;
@@ -1324,13 +1305,13 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
 }
 
 GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void **tables, void *ctx) {
-    if (!d || !tables || !ctx) return fail("null pointer");
+    if (!d || !tables || !ctx) return fail(GL_E_INVALID, "null pointer");
     if (d->struct_size != sizeof(GlStarkTablesDesc))
-        return fail("GlStarkTablesDesc.struct_size does not equal sizeof(GlStarkTablesDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
-    if (!d->num_tables || !d->tables) return fail("no tables");
+        return fail(GL_E_INVALID, "GlStarkTablesDesc.struct_size does not equal sizeof(GlStarkTablesDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+    if (!d->num_tables || !d->tables) return fail(GL_E_INVALID, "no tables");
     if (!d->num_lookups || !d->num_twcs || !d->h_lookup_bounds || !d->h_twc_table || !d->h_twc_column_bounds || !d->h_twc_filter || !d->h_column_bounds ||
         (d->num_ctl_columns && !d->h_column_constants))
-        return fail("No CTL? (null or empty cross-table lookup arrays)");
+        return fail(GL_E_INVALID, "No CTL? (null or empty cross-table lookup arrays)");
     const uint32_t nt = d->num_tables, ncol = d->num_ctl_columns, ntw = d->num_twcs, nl = d->num_lookups;
     auto bounds_ok = [](const uint32_t *b, uint32_t count, uint32_t limit) {
         if (b[0] != 0) return false;
@@ -1338,19 +1319,19 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
             if (b[i + 1] < b[i]) return false;
         return b[count] <= limit;
     };
-    if (!bounds_ok(d->h_column_bounds, ncol, 0xFFFFFFFFu)) return fail("h_column_bounds must start at 0 and not decrease");
+    if (!bounds_ok(d->h_column_bounds, ncol, 0xFFFFFFFFu)) return fail(GL_E_INVALID, "h_column_bounds must start at 0 and not decrease");
     const uint32_t nterms = d->h_column_bounds[ncol];
-    if (nterms && (!d->h_term_columns || !d->h_term_coeffs)) return fail("null pointer");
-    if (!bounds_ok(d->h_twc_column_bounds, ntw, ncol)) return fail("h_twc_column_bounds must start at 0, not decrease and stay within the CTL columns");
-    if (!bounds_ok(d->h_lookup_bounds, nl, ntw)) return fail("h_lookup_bounds must start at 0, not decrease and stay within the TWCs");
+    if (nterms && (!d->h_term_columns || !d->h_term_coeffs)) return fail(GL_E_INVALID, "null pointer");
+    if (!bounds_ok(d->h_twc_column_bounds, ntw, ncol)) return fail(GL_E_INVALID, "h_twc_column_bounds must start at 0, not decrease and stay within the CTL columns");
+    if (!bounds_ok(d->h_lookup_bounds, nl, ntw)) return fail(GL_E_INVALID, "h_lookup_bounds must start at 0, not decrease and stay within the TWCs");
     const uint32_t nch = d->tables[0].num_challenges;
     for (uint32_t k = 0; k < nt; k++) {
         const GlStarkDesc &t = d->tables[k], &t0 = d->tables[0];
-        if (t.struct_size != sizeof(GlStarkDesc)) return fail("GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
+        if (t.struct_size != sizeof(GlStarkDesc)) return fail(GL_E_INVALID, "GlStarkDesc.struct_size does not equal sizeof(GlStarkDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
         if (t.num_challenges != t0.num_challenges || t.fri.rate_bits != t0.fri.rate_bits || t.fri.cap_height != t0.fri.cap_height ||
             t.fri.proof_of_work_bits != t0.fri.proof_of_work_bits || t.fri.num_query_rounds != t0.fri.num_query_rounds || (t.fri.hiding != 0) != (t0.fri.hiding != 0))
-            return fail("table " + std::to_string(k) + ": the tables share one StarkConfig (num_challenges, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, hiding); only reduction_arity_bits may differ");
-        if (t.num_public_inputs) return fail("table " + std::to_string(k) + ": a table of a multi-table STARK has no public inputs");
+            return fail(GL_E_INVALID, "table " + std::to_string(k) + ": the tables share one StarkConfig (num_challenges, rate_bits, cap_height, proof_of_work_bits, num_query_rounds, hiding); only reduction_arity_bits may differ");
+        if (t.num_public_inputs) return fail(GL_E_INVALID, "table " + std::to_string(k) + ": a table of a multi-table STARK has no public inputs");
     }
     // a CTL column as used by a TWC of table `table`: its terms name columns of that table
     auto column_ok = [&](uint32_t col, uint32_t table) {
@@ -1359,37 +1340,37 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
         return true;
     };
     for (uint32_t t = 0; t < ntw; t++) {
-        if (d->h_twc_table[t] >= nt) return fail("TWC " + std::to_string(t) + ": table out of range");
-        if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && d->h_twc_filter[t] >= ncol) return fail("TWC " + std::to_string(t) + ": filter column out of range");
+        if (d->h_twc_table[t] >= nt) return fail(GL_E_INVALID, "TWC " + std::to_string(t) + ": table out of range");
+        if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && d->h_twc_filter[t] >= ncol) return fail(GL_E_INVALID, "TWC " + std::to_string(t) + ": filter column out of range");
         for (uint32_t k = d->h_twc_column_bounds[t]; k < d->h_twc_column_bounds[t + 1]; k++)
-            if (!column_ok(k, d->h_twc_table[t])) return fail("TWC " + std::to_string(t) + ": a term's column is out of range for its table");
+            if (!column_ok(k, d->h_twc_table[t])) return fail(GL_E_INVALID, "TWC " + std::to_string(t) + ": a term's column is out of range for its table");
         if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && !column_ok(d->h_twc_filter[t], d->h_twc_table[t]))
-            return fail("TWC " + std::to_string(t) + ": a term's column of the filter is out of range for its table");
+            return fail(GL_E_INVALID, "TWC " + std::to_string(t) + ": a term's column of the filter is out of range for its table");
     }
     std::vector<std::vector<uint32_t>> zs(nt);  // per table (twc, challenge), cross_table_lookup_data's order
     std::vector<bool> filtered(nt, false), unfiltered(nt, false);
     for (uint32_t l = 0; l < nl; l++) {
         const uint32_t lo = d->h_lookup_bounds[l], hi = d->h_lookup_bounds[l + 1];
-        if (hi - lo < 2) return fail("lookup " + std::to_string(l) + ": a lookup has at least one looking table and the looked table");
+        if (hi - lo < 2) return fail(GL_E_INVALID, "lookup " + std::to_string(l) + ": a lookup has at least one looking table and the looked table");
         const uint32_t width = d->h_twc_column_bounds[lo + 1] - d->h_twc_column_bounds[lo];
         const bool has_filter = d->h_twc_filter[lo] != GL_CTL_NO_FILTER;
         for (uint32_t t = lo; t < hi; t++) {
-            if (d->h_twc_column_bounds[t + 1] - d->h_twc_column_bounds[t] != width) return fail("lookup " + std::to_string(l) + ": its tables have unequal numbers of columns");
+            if (d->h_twc_column_bounds[t + 1] - d->h_twc_column_bounds[t] != width) return fail(GL_E_INVALID, "lookup " + std::to_string(l) + ": its tables have unequal numbers of columns");
             if ((d->h_twc_filter[t] != GL_CTL_NO_FILTER) != has_filter)
-                return fail("lookup " + std::to_string(l) + ": either every table of a lookup has a filter column or none has (CrossTableLookup::new)");
+                return fail(GL_E_INVALID, "lookup " + std::to_string(l) + ": either every table of a lookup has a filter column or none has (CrossTableLookup::new)");
             (has_filter ? filtered : unfiltered)[d->h_twc_table[t]] = true;
         }
         for (uint32_t c = 0; c < nch; c++)
             for (uint32_t t = lo; t < hi; t++) zs[d->h_twc_table[t]].push_back(t), zs[d->h_twc_table[t]].push_back(c);
     }
     for (uint32_t k = 0; k < nt; k++) {
-        if (zs[k].empty()) return fail("No CTL? (no lookup names table " + std::to_string(k) + ")");
-        if (filtered[k] && d->tables[k].constraint_degree < 3) return fail("table " + std::to_string(k) + ": the checks of a filtered CTL Z have degree 3: constraint_degree must be at least 3");
-        if (d->tables[k].constraint_degree < 2) return fail("table " + std::to_string(k) + ": the checks of a CTL Z have degree 2: constraint_degree must be at least 2");
+        if (zs[k].empty()) return fail(GL_E_INVALID, "No CTL? (no lookup names table " + std::to_string(k) + ")");
+        if (filtered[k] && d->tables[k].constraint_degree < 3) return fail(GL_E_INVALID, "table " + std::to_string(k) + ": the checks of a filtered CTL Z have degree 3: constraint_degree must be at least 3");
+        if (d->tables[k].constraint_degree < 2) return fail(GL_E_INVALID, "table " + std::to_string(k) + ": the checks of a CTL Z have degree 2: constraint_degree must be at least 2");
         TRY(stark_check(hasher, &d->tables[k], (uint32_t)zs[k].size() / 2));
     }
     const plonky2_hip::NttTables *tb;
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     StarkTables *T = new StarkTables();
     auto bail = [&](GlError e) {
         delete T;
@@ -1437,7 +1418,7 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
 void gl_stark_tables_destroy(void *tables) { delete static_cast<StarkTables *>(tables); }
 
 GlError gl_stark_tables_trim(void *tables) {
-    if (!tables) return fail("null pointer");
+    if (!tables) return fail(GL_E_INVALID, "null pointer");
     StarkTables *T = static_cast<StarkTables *>(tables);
     for (Stark *s : T->tables) TRY(s->trim());
     return T->trim();
@@ -1447,23 +1428,23 @@ GlError gl_stark_tables_trim(void *tables) {
 static GlError tables_ctl_zs(const StarkTables &T, uint32_t k, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_ctl_challenges,
                              uint64_t *d_zs, uint64_t *d_flag, void *ctx) {
     const plonky2_hip::NttTables *tb;
-    if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+    TRY(tables_of(ctx, &tb));
     const hipError_t e = plonky2_hip::stark_ctl_zs(*tb, d_trace, trace_stride, T.ctl(k), h_ctl_challenges, T.num_challenges, T.tables[k]->degree_bits, d_zs,
-                                                   d_flag, *reinterpret_cast<hipStream_t *>(ctx));
-    if (e == hipErrorInvalidValue) return fail("inconsistent arguments of the CTL Zs (trace_stride / sizes / more Zs than the context's scratch holds block totals for)");
+                                                   d_flag, ctx_stream(ctx));
+    if (e == hipErrorInvalidValue) return fail(GL_E_INVALID, "inconsistent arguments of the CTL Zs (trace_stride / sizes / more Zs than the context's scratch holds block totals for)");
     if (e != hipSuccess) return hip_fail(e, "stark_ctl_zs");
     return ok();
 }
 
 GlError gl_stark_tables_ctl_zs(const void *tables, uint32_t table, const uint64_t *d_trace, uint64_t trace_stride, const uint64_t *h_ctl_challenges,
                                uint64_t *d_zs, void *ctx) {
-    if (!tables || !d_trace || !h_ctl_challenges || !d_zs || !ctx) return fail("null pointer");
+    if (!tables || !d_trace || !h_ctl_challenges || !d_zs || !ctx) return fail(GL_E_INVALID, "null pointer");
     const StarkTables &T = *static_cast<const StarkTables *>(tables);
-    if (table >= T.tables.size()) return fail("table out of range");
-    if (trace_stride < (1ull << T.tables[table]->degree_bits)) return fail("trace_stride smaller than the column length");
+    if (table >= T.tables.size()) return fail(GL_E_INVALID, "table out of range");
+    if (trace_stride < (1ull << T.tables[table]->degree_bits)) return fail(GL_E_INVALID, "trace_stride smaller than the column length");
     {
         const plonky2_hip::NttTables *tb;
-        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+        TRY(tables_of(ctx, &tb));
     }
     DevBuf flag;
     TRY(flag.alloc(1));
@@ -1471,16 +1452,16 @@ GlError gl_stark_tables_ctl_zs(const void *tables, uint32_t table, const uint64_
     TRY(tables_ctl_zs(T, table, d_trace, trace_stride, h_ctl_challenges, d_zs, flag.p, ctx));
     uint64_t h_flag = 0;
     TRY(gl_memcpy_d2h(&h_flag, flag.p, 8, ctx));  // synchronous
-    if (h_flag) return fail("Non-binary filter?");
+    if (h_flag) return fail(GL_E_INVALID, "Non-binary filter?");
     return ok();
 }
 
 GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const uint64_t *d_trace_lde, const uint64_t *d_zs_lde,
                                        uint64_t column_stride, const uint64_t *h_alphas, const uint64_t *h_perm_challenges,
                                        const uint64_t *h_ctl_challenges, uint64_t *d_quotient_polys, void *ctx) {
-    if (!tables || !d_trace_lde || !d_zs_lde || !h_alphas || !h_ctl_challenges || !d_quotient_polys || !ctx) return fail("null pointer");
+    if (!tables || !d_trace_lde || !d_zs_lde || !h_alphas || !h_ctl_challenges || !d_quotient_polys || !ctx) return fail(GL_E_INVALID, "null pointer");
     const StarkTables &T = *static_cast<const StarkTables *>(tables);
-    if (table >= T.tables.size()) return fail("table out of range");
+    if (table >= T.tables.size()) return fail(GL_E_INVALID, "table out of range");
     const plonky2_hip::StarkCtlDev ctl = T.ctl(table);
     return quotient_polys_call(*T.tables[table], d_trace_lde, d_zs_lde, column_stride, h_alphas, h_perm_challenges, nullptr, d_quotient_polys, ctx, &ctl,
                                h_ctl_challenges);
@@ -1488,14 +1469,14 @@ GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const
 
 GlError gl_stark_tables_prove(const void *tables, const uint64_t *const *d_traces, uint8_t **proof, uint64_t *proof_len, double *h_stage_ms,
                               void *ctx) {
-    if (!tables || !d_traces || !proof || !proof_len || !ctx) return fail("null pointer");
+    if (!tables || !d_traces || !proof || !proof_len || !ctx) return fail(GL_E_INVALID, "null pointer");
     const StarkTables &T = *static_cast<const StarkTables *>(tables);
     const uint32_t nt = (uint32_t)T.tables.size(), nch = T.num_challenges;
     for (uint32_t k = 0; k < nt; k++)
-        if (!d_traces[k]) return fail("null trace");
+        if (!d_traces[k]) return fail(GL_E_INVALID, "null trace");
     {
         const plonky2_hip::NttTables *tb;
-        if (hipError_t e = plonky2_hip::ctx_tables(ctx, &tb); e != hipSuccess) return hip_fail(e, "context tables");
+        TRY(tables_of(ctx, &tb));
     }
     Pool *pool = T.pool_of(ctx);
     PoolScope pool_scope(pool);  // the trace commitments, the CTL Zs and the shared small data; every table's own buffers: its Stark's pool

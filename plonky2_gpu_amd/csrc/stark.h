@@ -76,7 +76,4 @@ struct StarkQuotientArgs {
 // starky/src/prover.rs:199-319 up to the coset_ifft)
 hipError_t stark_quotient_values(const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream);
 
-// capi.hip: makes the device of `ctx` current and returns its tables and workspace
-hipError_t ctx_tables(void *ctx, const NttTables **out);
-
 }  // namespace plonky2_hip

@@ -384,8 +384,7 @@ hipError_t stark_ctl_zs(const NttTables &tb, const uint64_t *trace, uint64_t tra
 }
 
 hipError_t stark_quotient_values(const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream) {
-    uint32_t qdb = 0;
-    while ((1u << qdb) < a.qdf) qdb++;  // log2_ceil
+    const uint32_t qdb = glh::log2_ceil(a.qdf);
     if (a.num_challenges == 0 || a.num_challenges > STARK_MAX_CHALLENGES || a.qdf == 0 || a.qdf > STARK_MAX_QDF || qdb > a.rate_bits ||
         a.degree_bits + a.rate_bits > 24 || a.column_stride < (1ull << (a.degree_bits + a.rate_bits)) || !a.alphas)
         return hipErrorInvalidValue;

@@ -1,4 +1,4 @@
-"""Contexts on one device since round 6 (csrc/capi.hip CtxState): each owns its workspace, event pair and hashing stream, so that
+"""Contexts on one device since round 6 (csrc/ctx.h CtxState): each owns its workspace, event pair and hashing stream, so that
 several run at the same time; the reference's memory contract as an option (caller-provided workspace and staging buffer,
 fri/oracle.rs:94-106: the caller sizes every device buffer up front); a public-inputs hash per context; contexts the caller
 builds from its own streams (the reference's CudaInnerContext, fri/oracle.rs:43-47)."""
@@ -40,7 +40,7 @@ def _free_bytes(hip):
 @pytest.mark.gpu
 def test_a_second_context_is_not_queued_behind_the_first(gpu, oracle):
     """Up to round 5 every call took a per-device lock and made its stream wait for whatever the OTHER context had queued
-    (capi.hip DeviceCall): a small transform on a second context finished when the first context's commit did. Now it
+    (ctx.h DeviceCall): a small transform on a second context finished when the first context's commit did. Now it
     finishes while that commit is still running — and both results are what they are alone."""
     import plonky2_gpu_amd as pg
     from plonky2_gpu_amd import _lib

@@ -78,7 +78,7 @@ def test_canonical_domain_asm_primitives(gpu):
 
 
 def _dotacc(mode, x, y):
-    """the accumulator capi.hip's dotacc_from() builds from two test words"""
+    """the accumulator probes.hip's dotacc_from() builds from two test words"""
     m64 = (1 << 64) - 1
     if mode == 0:
         return x, y, ((~x & m64) + ((y << 13) & m64)) & m64, y >> 59, x >> 58, (x ^ y) & 7

@@ -238,6 +238,105 @@ def test_commits_refuse_four_element_leaves_unknown_hashers_and_bad_shapes(gpu):
         pg.MerkleTree.new(gpu, np.zeros((4, 5), dtype=np.uint64), 0, hasher="blake")
 
 
+NULL_POINTER = "null pointer"
+UNKNOWN_HASHER = "unknown hasher"
+CAP_TOO_HIGH = "cap_height should be at most log2(leaves.len())"
+LOG_N_TOO_BIG = "log_n > 24 is not supported by this build"
+KECCAK_LEAF_LEN_4 = "KeccakHash<25>::hash_or_noop is undefined for leaves of 4 elements (plonk/config.rs:58-63 panics)"
+
+
+def _refused(name, args, message):
+    import plonky2_gpu_amd as pg
+    from plonky2_gpu_amd import _lib
+
+    with pytest.raises(pg.Plonky2HipError) as e:
+        _lib.call(name, *args)
+    assert e.value.code == pg.GL_E_INVALID
+    assert str(e.value) == "plonky2_hip error %d: %s" % (pg.GL_E_INVALID, message), name
+
+
+# (entry point, hasher); None: the un-suffixed entry point, which takes no hasher and commits with Poseidon
+@pytest.mark.parametrize("name,hasher", [("gl_commit_from_coeffs", None), ("gl_commit_from_values", None)] +
+                         [(n, h) for n in ("gl_commit_from_coeffs_h", "gl_commit_from_values_h") for h in (POSEIDON, KECCAK)])
+def test_each_refusal_of_a_commit_has_its_message(gpu, name, hasher):
+    """one broken rule per call, on the tiny shape of the test above: GL_E_INVALID with the message of that rule, the same for
+    every entry point and hasher that has the rule. A null d_digests is what the hashers treat differently: Poseidon refuses it
+    always, Keccak takes it exactly when the tree is all cap (cap_height == log_n + rate_bits)."""
+    from plonky2_gpu_amd import _lib
+
+    log_n, rate_bits, h, polys = 5, 1, 2, 3
+    n, n_ext = 1 << log_n, 1 << (log_n + rate_bits)
+    vals = np.random.default_rng(7).integers(0, P, size=(polys, n), dtype=np.uint64)
+    bufs = dict(d_in=_buf(gpu, vals), d_lde=_buf(gpu, polys * n_ext), d_lv=_buf(gpu, polys * n_ext), d_dig=_buf(gpu, 8 * n_ext),
+                d_cap=_buf(gpu, 4 * n_ext))
+
+    def args(hasher=hasher, polys=polys, log_n=log_n, cap_h=h, salt=0, **null):
+        p = {k: (None if k in null else b.ptr) for k, b in bufs.items()}
+        a = (p["d_in"], polys, log_n, rate_bits, cap_h, salt, 7, p["d_lde"], p["d_lv"], p["d_dig"], p["d_cap"], gpu.ptr)
+        return a if name[-2:] != "_h" else (hasher,) + a
+
+    _refused(name, args(d_lde=None), NULL_POINTER)
+    _refused(name, args(d_cap=None), NULL_POINTER)
+    _refused(name, args(d_dig=None), NULL_POINTER)
+    if hasher == KECCAK:
+        bufs["d_in"].upload(vals)
+        _lib.call(name, *args(cap_h=log_n + rate_bits, d_dig=None))
+        cap_without = bufs["d_cap"].download(0, 4 * n_ext)
+        bufs["d_in"].upload(vals)
+        _lib.call(name, *args(cap_h=log_n + rate_bits))
+        assert (bufs["d_cap"].download(0, 4 * n_ext) == cap_without).all()
+    else:
+        _refused(name, args(cap_h=log_n + rate_bits, d_dig=None), NULL_POINTER)
+    _refused(name, args(polys=0), "bad poly_num")
+    _refused(name, args(log_n=25), LOG_N_TOO_BIG)
+    _refused(name, args(cap_h=log_n + rate_bits + 1), CAP_TOO_HIGH)
+    if name[-2:] == "_h":
+        _refused(name, args(hasher=5), UNKNOWN_HASHER)
+    if hasher == KECCAK:
+        _refused(name, args(polys=0, salt=4), KECCAK_LEAF_LEN_4)
+    gpu.synchronize()
+    for b in bufs.values():
+        b.free()
+
+
+@pytest.mark.parametrize("name,hasher", [("gl_merkle_tree_from_columns", None), ("gl_merkle_tree_from_leaves", None)] +
+                         [(n, h) for n in ("gl_merkle_tree_from_columns_h", "gl_merkle_tree_from_leaves_h") for h in (POSEIDON, KECCAK)])
+def test_each_refusal_of_a_tree_has_its_message(gpu, name, hasher):
+    """the same for the four tree entry points. Only Keccak checks d_digests (refused when a layer lies below the cap); a tree
+    that is all cap takes a null d_digests with either hasher."""
+    from plonky2_gpu_amd import _lib
+
+    n, k, h = 16, 5, 2
+    columns = "columns" in name
+    leaves = np.random.default_rng(8).integers(0, P, size=(n, k), dtype=np.uint64)
+    bufs = dict(d_in=_buf(gpu, leaves), d_dig=_buf(gpu, 4 * _n_digest_slots(n, h)), d_cap=_buf(gpu, 4 * n))
+
+    def args(hasher=hasher, k=k, n=n, col_stride=n, cap_h=h, **null):
+        p = {key: (None if key in null else b.ptr) for key, b in bufs.items()}
+        a = (p["d_in"], k, n) + ((col_stride,) if columns else ()) + (cap_h, p["d_dig"], p["d_cap"], gpu.ptr)
+        return a if name[-2:] != "_h" else (hasher,) + a
+
+    _refused(name, args(d_in=None), NULL_POINTER)
+    _refused(name, args(d_cap=None), NULL_POINTER)
+    if hasher == KECCAK:
+        _refused(name, args(d_dig=None), NULL_POINTER)
+    _lib.call(name, *args(cap_h=4, d_dig=None))
+    cap_without = bufs["d_cap"].download(0, 4 * n)
+    _lib.call(name, *args(cap_h=4))
+    assert (bufs["d_cap"].download(0, 4 * n) == cap_without).all()
+    _refused(name, args(n=3, cap_h=1), "n_leaves must be a power of two")
+    _refused(name, args(cap_h=5), CAP_TOO_HIGH)
+    if columns:
+        _refused(name, args(col_stride=n - 1), "col_stride smaller than n_leaves: the columns would overlap")
+    if name[-2:] == "_h":
+        _refused(name, args(hasher=5), UNKNOWN_HASHER)
+    if hasher == KECCAK:
+        _refused(name, args(k=4), KECCAK_LEAF_LEN_4)
+    gpu.synchronize()
+    for b in bufs.values():
+        b.free()
+
+
 # ---- openings ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("log_n,k,h,which", [(10, 7, 2, "all"), (16, 20, 4, "random")])

@@ -127,6 +127,29 @@ def test_merkle_cap_height_too_big(gpu, oracle):
     assert e.value.code == pg.GL_E_INVALID
 
 
+@pytest.mark.parametrize("name,hasher", [("gl_commit_from_values", None), ("gl_commit_from_values_h", 0), ("gl_commit_from_values_h", 1)])
+def test_a_refused_commit_from_values_leaves_the_values_untouched(gpu, oracle, name, hasher):
+    """cap_height 5 above log_n + rate_bits = 4: refused with the tree's message before the inverse NTT runs in place, so d_values
+    reads back word for word, with Poseidon as with Keccak (hasher 1)"""
+    import plonky2_gpu_amd as pg
+    from plonky2_gpu_amd import _lib
+
+    log_n, rate_bits, polys, h = 3, 1, 2, 5
+    n_ext = 1 << (log_n + rate_bits)
+    vals = oracle.random_field((polys, 1 << log_n), seed=31)
+    d_v = pg.DeviceBuffer.from_host(gpu, vals)
+    d_lde, d_lv, d_dig, d_cap = (pg.DeviceBuffer(gpu, words) for words in (polys * n_ext, polys * n_ext, 8 * n_ext, 4 << h))
+    args = (d_v.ptr, polys, log_n, rate_bits, h, 0, 7, d_lde.ptr, d_lv.ptr, d_dig.ptr, d_cap.ptr, gpu.ptr)
+    with pytest.raises(pg.Plonky2HipError) as e:
+        _lib.call(name, *(args if hasher is None else (hasher,) + args))
+    assert e.value.code == pg.GL_E_INVALID
+    assert str(e.value) == "plonky2_hip error %d: cap_height should be at most log2(leaves.len())" % pg.GL_E_INVALID
+    gpu.synchronize()
+    assert (d_v.download() == vals.reshape(-1)).all(), "a refused commit transformed its input"
+    for b in (d_v, d_lde, d_lv, d_dig, d_cap):
+        b.free()
+
+
 @pytest.mark.parametrize("n_polys,log_n,rate_bits,h", [(5, 4, 3, 2), (135, 6, 3, 4), (3, 0, 3, 1), (20, 10, 3, 4), (2, 13, 3, 4),
                                                        (16, 14, 1, 0), (234, 8, 3, 4), (4, 5, 3, 8), (9, 12, 2, 4)])
 def test_commit_from_values_matches_oracle(gpu, oracle, n_polys, log_n, rate_bits, h):
@@ -168,7 +191,7 @@ def test_commit_from_values_matches_oracle(gpu, oracle, n_polys, log_n, rate_bit
 )
 def test_commit_through_the_pipelined_path(gpu, oracle, n_polys, log_n, rate_bits, h, leaf_major, salted):
     """From 48 columns and 2^16 leaves on, the commit runs the LDE in chunks of 16 columns on the caller's stream while a second
-    stream absorbs each finished chunk into the leaves' sponges (capi.hip commit_from_coeffs_impl; the capacity words wait in the
+    stream absorbs each finished chunk into the leaves' sponges (commit.hip commit_from_coeffs; the capacity words wait in the
     digest slot between launches). Same answers as the one-shot path's oracle: coefficients, LDE, digests, cap, leaf-major copy,
     for chunk counts and leftovers of every kind, with and without salt columns."""
     import plonky2_gpu_amd as pg

@@ -254,7 +254,7 @@ def test_coset_fft_and_ifft_natural_order(gpu, oracle, log_n):
 
 
 def test_more_distinct_cosets_than_the_table_cache_holds(gpu, oracle):
-    """The per-device coset-table cache (capi.hip get_coset_tables) is a bounded LRU: a process that has used
+    """The per-device coset-table cache (ctx.hip get_coset_tables) is a bounded LRU: a process that has used
     more distinct (size, rate, shift) combinations than it holds must keep working and keep being right,
     including for a combination that was evicted and is built again. 150 shifts x (forward + inverse tables)
     is several times the bound whatever ran earlier in this process."""

@@ -498,7 +498,7 @@ def test_two_host_threads_with_their_own_contexts_on_one_device(gpu):
     """Two threads, each with its own context, circuit and data, hammering natural-order transforms (which stage through the
     workspace), commits with the leaf-major copy (the event pair) and whole proofs at the same time must each get exactly the
     results they get alone. Up to round 5 the workspace and the event pair existed once per device and the entry points took
-    turns (a per-device lock); since round 6 they belong to the context (capi.hip CtxState) and the two threads' calls really
+    turns (a per-device lock); since round 6 they belong to the context (ctx.h CtxState) and the two threads' calls really
     run at the same time — tests/test_gpu_contexts.py holds that they do."""
     import threading
 

@@ -6,7 +6,7 @@ values_device, ..)` -- region A passed both as the coefficients and as the place
 call returns the host READS the copy's destination (:462). from_coeffs_with_gpu does the same without the ifft (:595-640).
 The reference's body honours this with cudaStreamSynchronize(ctx->stream2) before its transposition overwrites region A
 (cuda/plonky2_gpu.cu:586). Here the order is an event recorded on stream2 that the hashing / transposing stream waits for
-(csrc/capi.hip commit_from_coeffs_impl) plus a final wait for stream2 in the symbol.
+(csrc/commit.hip commit_from_coeffs) plus a final wait for stream2 in the symbol.
 
 stream2 is kept busy with earlier copies so that, without that order, the leaves WOULD be written long before the copy of the
 coefficients runs: with PLONKY2_DROP_STREAM2_WAIT=1 in the diagnostic build these tests fail (tools/gpu_runs/stream2_negative.sh

@@ -1,5 +1,5 @@
 """Proofs per second of ONE GPU with K proofs in flight (configs[4]'s per-GPU factor): K host threads, each with its own context
-(its own streams, workspace, hashing stream: csrc/capi.hip CtxState) and — by default — its own circuit handle, prove the
+(its own streams, workspace, hashing stream: csrc/ctx.h CtxState) and — by default — its own circuit handle, prove the
 ed25519-shaped synthetic circuit of tools/bench_prove.py back to back. A proof has latency-bound phases (the transcript's serial
 sponge, tree layers below 2^16 nodes, openings, host round trips) during which one proof alone leaves the chip idle; a second proof
 in flight fills them. Every proof's bytes are compared with the bytes the same witness gives alone on one context.
