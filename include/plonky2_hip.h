@@ -721,6 +721,31 @@ GlError gl_stark_tables_quotient_polys(const void *tables, uint32_t table, const
                                        uint64_t column_stride, const uint64_t *h_alphas, const uint64_t *h_perm_challenges,
                                        const uint64_t *h_ctl_challenges, uint64_t *d_quotient_polys, void *ctx);
 
+/* ---- A STARK's constraints compiled into a kernel of their own (opt-in) ----------------------------
+ * By default the quotient INTERPRETS the register program per LDE point. gl_stark_compile turns the handle's description — the
+ * program, the permutation checks and, for a table, its CTL checks — into straight-line HIP source for one kernel specialised to
+ * that STARK (registers in VGPRs, immediates, ACC weights, column indices, CTL terms and coefficients as literals), compiles it
+ * with hiprtc for gfx950 and uses it from then on wherever the handle computes a quotient. The values are the interpreter's bit
+ * for bit. Code objects are kept where the gate kernels' are: $PLONKY2_HIP_KERNEL_CACHE (empty = no cache), else the directory
+ * kernel_cache next to the library if it exists; files stark_<hash of source, hiprtc version, target>.hsaco with the source in
+ * .hip next to it; $PLONKY2_HIP_KERNEL_CACHE_LIST receives their paths. A compiled handle is used by several host threads on
+ * several contexts at once, as an interpreted one.
+ *
+ * Compile the handle's quotient kernel(s) and use them from now on in gl_stark_prove / gl_stark_quotient_polys
+ * (gl_stark_tables_prove / gl_stark_tables_quotient_polys). Only between proofs, like gl_stark_trim. A second call is a no-op.
+ * On failure (hiprtc / module load) the message carries the compiler's log and the handle stays interpreted and usable. */
+GlError gl_stark_compile(void *stark, void *ctx);
+GlError gl_stark_tables_compile(void *tables, void *ctx); /* one kernel per table; compile side by side, at most 8 threads */
+int gl_stark_is_compiled(const void *stark);
+int gl_stark_tables_is_compiled(const void *tables);
+const char *gl_stark_kernel_source(const void *stark); /* NULL unless compiled */
+const char *gl_stark_tables_kernel_source(const void *tables, uint32_t table);
+/* Device-free: validate exactly as gl_stark_create / gl_stark_tables_create do, generate, compile into the kernel cache.
+ * No context, no allocation, no module load — what a build machine without a GPU runs so that *_compile finds its kernels.
+ * GL_E_INVALID also where there is no kernel cache to compile into. */
+GlError gl_stark_precompile(uint32_t hasher, const GlStarkDesc *desc);
+GlError gl_stark_tables_precompile(uint32_t hasher, const GlStarkTablesDesc *desc);
+
 /* ---------------------------------------------------------------------------------------------
  * The lookup columns of a trace: the Halo2-style lookup argument of the reference's STARKs (evm/src/lookup.rs, used by its memory
  * table, memory_stark.rs:147, and by system_zero/src/lookup.rs). A lookup is four trace columns: the inputs, the table, and the

@@ -339,6 +339,16 @@ class Stark {
         return out;
     }
     void trim() const { check(gl_stark_trim(ptr_)); }
+    // gl_stark_compile: from now on the quotient runs a kernel generated from this STARK's description (the same values); only
+    // between proofs. Throws with the compiler's log on failure; the handle then stays interpreted and usable.
+    void compile(const Context &ctx) { check(gl_stark_compile(ptr_, ctx.get())); }
+    bool is_compiled() const { return gl_stark_is_compiled(ptr_) != 0; }
+    std::string kernel_source() const {
+        const char *src = gl_stark_kernel_source(ptr_);
+        return src ? src : "";
+    }
+    // gl_stark_precompile: validate, generate and compile into the kernel cache without a device (a build machine's step)
+    static void precompile(const GlStarkDesc &desc, Hasher hasher = Hasher::Poseidon) { check(gl_stark_precompile((uint32_t)hasher, &desc)); }
 
   private:
     void *ptr_ = nullptr;
@@ -369,6 +379,16 @@ class StarkTables {
         return out;
     }
     void trim() const { check(gl_stark_tables_trim(ptr_)); }
+    // gl_stark_tables_compile: one generated quotient kernel per table, as Stark::compile; all tables or none
+    void compile(const Context &ctx) { check(gl_stark_tables_compile(ptr_, ctx.get())); }
+    bool is_compiled() const { return gl_stark_tables_is_compiled(ptr_) != 0; }
+    std::string kernel_source(uint32_t table) const {
+        const char *src = gl_stark_tables_kernel_source(ptr_, table);
+        return src ? src : "";
+    }
+    static void precompile(const GlStarkTablesDesc &desc, Hasher hasher = Hasher::Poseidon) {
+        check(gl_stark_tables_precompile((uint32_t)hasher, &desc));
+    }
 
   private:
     void *ptr_ = nullptr;

@@ -248,6 +248,14 @@ SIGNATURES = {
     "gl_stark_tables_prove": (GlError, [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _vp, _vp]),
     "gl_stark_tables_ctl_zs": (GlError, [_vp, _u32, _vp, _u64, _vp, _vp, _vp]),
     "gl_stark_tables_quotient_polys": (GlError, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gl_stark_compile": (GlError, [_vp, _vp]),
+    "gl_stark_tables_compile": (GlError, [_vp, _vp]),
+    "gl_stark_is_compiled": (ctypes.c_int, [_vp]),
+    "gl_stark_tables_is_compiled": (ctypes.c_int, [_vp]),
+    "gl_stark_kernel_source": (ctypes.c_char_p, [_vp]),
+    "gl_stark_tables_kernel_source": (ctypes.c_char_p, [_vp, _u32]),
+    "gl_stark_precompile": (GlError, [_u32, ctypes.POINTER(GlStarkDesc)]),
+    "gl_stark_tables_precompile": (GlError, [_u32, ctypes.POINTER(GlStarkTablesDesc)]),
     "gl_lookup_scratch_bytes": (_u64, [_u64]),
     "gl_sort_canonical": (GlError, [_vp, _vp, _u64, _vp, _vp]),
     "gl_lookup_permuted_cols": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),

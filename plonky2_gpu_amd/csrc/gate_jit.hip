@@ -904,9 +904,12 @@ static uint32_t jit_unit_limit() {
     return hw == 0 ? 4 : hw > 8 ? 8 : hw;
 }
 
-// Cache file name of a unit (kernel_cache_dir()): keyed by a hash of the generated source and of what turns the same source
-// into a different code object — the hiprtc version and the target.
-static std::string unit_cache_path(const std::string &dir, const std::string &source) {
+// Cache file name of a compiled source (kernel_cache_dir()): keyed by a hash of the generated source and of what turns the same
+// source into a different code object — the hiprtc version and the target. `prefix`: "gate_" for a circuit's units, "stark_" for a
+// STARK's quotient kernel (stark_jit.hip).
+std::string jit_cache_dir() { return kernel_cache_dir(); }
+
+std::string jit_cache_path(const std::string &dir, const std::string &source, const char *prefix) {
     if (dir.empty()) return "";
     int rtc_major = 0, rtc_minor = 0;
     (void)hiprtcVersion(&rtc_major, &rtc_minor);
@@ -915,16 +918,34 @@ static std::string unit_cache_path(const std::string &dir, const std::string &so
     for (unsigned char ch : salt) h = (h ^ ch) * 0x100000001b3ull;
     for (unsigned char ch : source) h = (h ^ ch) * 0x100000001b3ull;
     char name[64];
-    snprintf(name, sizeof name, "/gate_%016llx", (unsigned long long)h);
+    snprintf(name, sizeof name, "/%s%016llx", prefix, (unsigned long long)h);
     return dir + name;
 }
 
-// hiprtc on one unit's source; the code object (and the source, for inspection) goes to the cache. Runs on a thread of its own.
-static bool compile_unit(GateUnit &u, const std::string &cache_path) {
+// $PLONKY2_HIP_KERNEL_CACHE_LIST=<file>: the cache entries this build uses, one path per line (appended) — how build() tells the
+// current generator's units from whatever else the cache directory holds without compiling anything twice (__graft_entry__.py)
+void jit_cache_list(const std::vector<std::string> &cache_paths) {
+    if (const char *lf = getenv("PLONKY2_HIP_KERNEL_CACHE_LIST"))
+        if (FILE *f = fopen(lf, "a")) {
+            for (const std::string &cp : cache_paths)
+                if (!cp.empty()) fprintf(f, "%s\n", cp.c_str());
+            fclose(f);
+        }
+}
+
+bool jit_cache_read(const std::string &cache_path, std::vector<char> *code) {
+    if (cache_path.empty()) return false;
+    std::ifstream f(cache_path + ".hsaco", std::ios::binary);
+    if (f) code->assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    return !code->empty();
+}
+
+// hiprtc on one source; the code object (and the source, for inspection) goes to the cache. May run on a thread of its own.
+bool jit_compile(const std::string &source, const char *program_name, const std::string &cache_path, std::vector<char> *code, std::string *error) {
     hiprtcProgram prog;
-    hiprtcResult r = hiprtcCreateProgram(&prog, u.source.c_str(), "gate_constraints.hip", 0, nullptr, nullptr);
+    hiprtcResult r = hiprtcCreateProgram(&prog, source.c_str(), program_name, 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) {
-        u.error = std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r);
+        *error = std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r);
         return false;
     }
     const std::string arch = std::string("--offload-arch=") + JIT_ARCH;
@@ -935,32 +956,38 @@ static bool compile_unit(GateUnit &u, const std::string &cache_path) {
         hiprtcGetProgramLogSize(prog, &ls);
         std::string log(ls, '\0');
         if (ls) hiprtcGetProgramLog(prog, &log[0]);
-        u.error = std::string("hiprtcCompileProgram: ") + hiprtcGetErrorString(r) + "\n" + log.substr(0, 4000);
+        *error = std::string("hiprtcCompileProgram: ") + hiprtcGetErrorString(r) + "\n" + log.substr(0, 4000);
         hiprtcDestroyProgram(&prog);
         return false;
     }
     size_t cs = 0;
     hiprtcGetCodeSize(prog, &cs);
-    u.code.resize(cs);
-    hiprtcGetCode(prog, u.code.data());
+    code->resize(cs);
+    hiprtcGetCode(prog, code->data());
     hiprtcDestroyProgram(&prog);
     if (!cache_path.empty()) {
         // Several processes (one per GPU) may build the same circuit at once: each writes a file of its own and
         // renames it into place, so a reader sees either nothing or a whole code object.
-        const std::string pid = std::to_string((long long)getpid()) + "." + std::to_string((unsigned long long)(uintptr_t)&u);
+        const std::string pid = std::to_string((long long)getpid()) + "." + std::to_string((unsigned long long)(uintptr_t)code);
         const std::string tmp = cache_path + ".tmp." + pid, tmp_src = cache_path + ".hip." + pid;
-        std::ofstream(tmp_src) << u.source;
+        std::ofstream(tmp_src) << source;
         (void)rename(tmp_src.c_str(), (cache_path + ".hip").c_str());
         bool written = false;
         {
             std::ofstream f(tmp, std::ios::binary);
-            f.write(u.code.data(), (std::streamsize)u.code.size());
+            f.write(code->data(), (std::streamsize)code->size());
             f.flush();
             written = f.good();
         }
         if (!written || rename(tmp.c_str(), (cache_path + ".hsaco").c_str()) != 0) (void)remove(tmp.c_str());
     }
     return true;
+}
+
+static std::string unit_cache_path(const std::string &dir, const std::string &source) { return jit_cache_path(dir, source, "gate_"); }
+
+static bool compile_unit(GateUnit &u, const std::string &cache_path) {
+    return jit_compile(u.source, "gate_constraints.hip", cache_path, &u.code, &u.error);
 }
 
 static hipError_t load_unit(GateUnit &u) {
@@ -1120,20 +1147,8 @@ GateKernel *gate_kernel_build(const uint16_t *instrs, uint32_t num_instrs, const
         k->source += u.source;
         cache_paths.push_back(unit_cache_path(dir, u.source));
     }
-    // $PLONKY2_HIP_KERNEL_CACHE_LIST=<file>: the cache entries this build uses, one path per line (appended) — how build() tells the
-    // current generator's units from whatever else the cache directory holds without compiling anything twice (__graft_entry__.py)
-    if (const char *lf = getenv("PLONKY2_HIP_KERNEL_CACHE_LIST"))
-        if (FILE *f = fopen(lf, "a")) {
-            for (const std::string &cp : cache_paths)
-                if (!cp.empty()) fprintf(f, "%s\n", cp.c_str());
-            fclose(f);
-        }
-    auto from_cache = [&](size_t i) {
-        if (cache_paths[i].empty()) return false;
-        std::ifstream f(cache_paths[i] + ".hsaco", std::ios::binary);
-        if (f) k->units[i].code.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-        return !k->units[i].code.empty();
-    };
+    jit_cache_list(cache_paths);
+    auto from_cache = [&](size_t i) { return jit_cache_read(cache_paths[i], &k->units[i].code); };
     // Compile what the cache does not have. hiprtc serialises concurrent compilations of one process behind a lock of its own
     // (eight threads took the 68 s one thread takes), so every unit but the first goes to a forked child: the child runs
     // hiprtc only — nothing that touches a device — writes the code object to a file and leaves with _exit; the parent compiles

@@ -23,6 +23,7 @@
 #include "gate_jit.h"
 #include "gl_field.h"
 #include "stark.h"
+#include "stark_jit.h"
 
 using namespace plonky2_hip;
 
@@ -892,6 +893,11 @@ namespace {
 struct Stark : ProverShape {
     uint32_t num_columns = 0, num_public_inputs = 0, num_challenges = 0, qdf = 0, qdb = 0, num_instrs = 0, num_pairs = 0, num_zs = 0;
     DevBuf d_instrs, d_imms, d_column_pairs, d_pair_bounds;
+    // the description on the host, for gl_stark_compile's generator; jit: the compiled quotient kernel that replaces the interpreter
+    // from gl_stark_compile on (null: interpreted)
+    plonky2_hip::StarkJitDesc host;
+    plonky2_hip::StarkJitKernel *jit = nullptr;
+    ~Stark() { plonky2_hip::stark_jit_destroy(jit); }
     plonky2_hip::StarkPairsDev pairs() const {
         plonky2_hip::StarkPairsDev p;
         p.column_pairs = reinterpret_cast<const uint32_t *>(d_column_pairs.p), p.pair_bounds = reinterpret_cast<const uint32_t *>(d_pair_bounds.p);
@@ -917,7 +923,8 @@ GlError stark_quotient(const Stark &s, const uint64_t *d_trace_lde, const uint64
     a.alphas = h_alphas, a.challenges = h_challenges;
     a.num_challenges = s.num_challenges, a.qdf = s.qdf, a.degree_bits = s.degree_bits, a.rate_bits = s.rate_bits;
     if (ctl) a.ctl = *ctl, a.ctl_challenges = h_ctl_challenges;
-    const hipError_t e = plonky2_hip::stark_quotient_values(*tb, a, d_out, ctx_stream(ctx));
+    const hipError_t e = s.jit ? plonky2_hip::stark_jit_launch(s.jit, *tb, a, d_out, ctx_stream(ctx))
+                               : plonky2_hip::stark_quotient_values(*tb, a, d_out, ctx_stream(ctx));
     if (e == hipErrorInvalidValue) return fail(GL_E_INVALID, "inconsistent arguments of the STARK quotient (column_stride / challenges / sizes)");
     if (e != hipSuccess) return hip_fail(e, "stark_quotient_values");
     const uint32_t log_size = s.degree_bits + s.qdb;
@@ -976,6 +983,32 @@ GlError stark_check(uint32_t hasher, const GlStarkDesc *d, uint32_t num_ctl_zs) 
     return ok();
 }
 
+// after stark_check: what the generator of the compiled quotient kernel reads (stark_jit.h), without the CTL part
+plonky2_hip::StarkJitDesc stark_host_desc(const GlStarkDesc *d) {
+    plonky2_hip::StarkJitDesc h;
+    const uint16_t *instrs = reinterpret_cast<const uint16_t *>(d->h_instrs);
+    h.instrs.assign(instrs, instrs + 4ull * d->num_instrs);
+    for (uint32_t i = 0; i < d->num_immediates; i++) h.imms.push_back(d->h_immediates[i] % P);
+    h.num_challenges = d->num_challenges, h.qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;
+    if (d->num_pairs) {
+        h.pair_bounds.assign(d->h_pair_bounds, d->h_pair_bounds + d->num_pairs + 1);
+        h.column_pairs.assign(d->h_column_pairs, d->h_column_pairs + 2ull * d->h_pair_bounds[d->num_pairs]);
+    }
+    return h;
+}
+
+// the CTL part of table k's description: the arrays of all tables and the table's own CTL Zs
+void stark_host_ctl(plonky2_hip::StarkJitDesc *h, const GlStarkTablesDesc *d, const std::vector<uint32_t> &zs) {
+    const uint32_t ncol = d->num_ctl_columns, ntw = d->num_twcs, nterms = d->h_column_bounds[ncol];
+    h->term_columns.assign(d->h_term_columns, d->h_term_columns + nterms);
+    for (uint32_t j = 0; j < nterms; j++) h->term_coeffs.push_back(d->h_term_coeffs[j] % P);
+    h->column_bounds.assign(d->h_column_bounds, d->h_column_bounds + ncol + 1);
+    for (uint32_t k = 0; k < ncol; k++) h->column_constants.push_back(d->h_column_constants[k] % P);
+    h->twc_column_bounds.assign(d->h_twc_column_bounds, d->h_twc_column_bounds + ntw + 1);
+    h->twc_filter.assign(d->h_twc_filter, d->h_twc_filter + ntw);
+    h->ctl_zs = zs;
+}
+
 // after stark_check
 GlError stark_build(uint32_t hasher, const GlStarkDesc *d, Stark **stark, void *ctx) {
     const uint32_t qdf = d->constraint_degree > 2 ? d->constraint_degree - 1 : 1;
@@ -989,6 +1022,7 @@ GlError stark_build(uint32_t hasher, const GlStarkDesc *d, Stark **stark, void *
     s->num_challenges = d->num_challenges, s->qdf = qdf, s->qdb = qdb, s->num_instrs = d->num_instrs, s->num_pairs = d->num_pairs;
     s->num_zs = d->num_pairs ? plonky2_hip::stark_num_zs(d->num_pairs, d->num_challenges, qdf) : 0;
     s->set_fri(d->fri);
+    s->host = stark_host_desc(d);
     auto bail = [&](GlError e) {
         delete s;
         return e;
@@ -1304,8 +1338,9 @@ GlError gl_stark_prove(const void *stark, const uint64_t *d_trace, const uint64_
     return bytes_out(out, proof, proof_len);
 }
 
-GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void **tables, void *ctx) {
-    if (!d || !tables || !ctx) return fail(GL_E_INVALID, "null pointer");
+// Everything gl_stark_tables_create refuses, before anything is allocated. zs: per table (twc, challenge) of its CTL Zs, in
+// cross_table_lookup_data's order.
+static GlError stark_tables_check(uint32_t hasher, const GlStarkTablesDesc *d, std::vector<std::vector<uint32_t>> *zs_out) {
     if (d->struct_size != sizeof(GlStarkTablesDesc))
         return fail(GL_E_INVALID, "GlStarkTablesDesc.struct_size does not equal sizeof(GlStarkTablesDesc) of this library: the caller was compiled against another version of include/plonky2_hip.h");
     if (!d->num_tables || !d->tables) return fail(GL_E_INVALID, "no tables");
@@ -1347,7 +1382,8 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
         if (d->h_twc_filter[t] != GL_CTL_NO_FILTER && !column_ok(d->h_twc_filter[t], d->h_twc_table[t]))
             return fail(GL_E_INVALID, "TWC " + std::to_string(t) + ": a term's column of the filter is out of range for its table");
     }
-    std::vector<std::vector<uint32_t>> zs(nt);  // per table (twc, challenge), cross_table_lookup_data's order
+    std::vector<std::vector<uint32_t>> &zs = *zs_out;
+    zs.assign(nt, {});
     std::vector<bool> filtered(nt, false), unfiltered(nt, false);
     for (uint32_t l = 0; l < nl; l++) {
         const uint32_t lo = d->h_lookup_bounds[l], hi = d->h_lookup_bounds[l + 1];
@@ -1369,6 +1405,15 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
         if (d->tables[k].constraint_degree < 2) return fail(GL_E_INVALID, "table " + std::to_string(k) + ": the checks of a CTL Z have degree 2: constraint_degree must be at least 2");
         TRY(stark_check(hasher, &d->tables[k], (uint32_t)zs[k].size() / 2));
     }
+    return ok();
+}
+
+GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void **tables, void *ctx) {
+    if (!d || !tables || !ctx) return fail(GL_E_INVALID, "null pointer");
+    std::vector<std::vector<uint32_t>> zs;  // per table (twc, challenge), cross_table_lookup_data's order
+    TRY(stark_tables_check(hasher, d, &zs));
+    const uint32_t nt = d->num_tables, ncol = d->num_ctl_columns, ntw = d->num_twcs, nterms = d->h_column_bounds[ncol];
+    const uint32_t nch = d->tables[0].num_challenges;
     const plonky2_hip::NttTables *tb;
     TRY(tables_of(ctx, &tb));
     StarkTables *T = new StarkTables();
@@ -1386,6 +1431,7 @@ GlError gl_stark_tables_create(uint32_t hasher, const GlStarkTablesDesc *d, void
     for (uint32_t k = 0; k < nt; k++) {
         Stark *s = nullptr;
         STRY(stark_build(hasher, &d->tables[k], &s, ctx));
+        stark_host_ctl(&s->host, d, zs[k]);
         T->tables.push_back(s);
     }
     auto upload32 = [&](DevBuf &b, const uint32_t *src, uint64_t count) -> GlError {
@@ -1531,6 +1577,94 @@ GlError gl_stark_tables_prove(const void *tables, const uint64_t *const *d_trace
         ctl_zs[k].reset();
     }
     return bytes_out(out, proof, proof_len);
+}
+
+// ---- the compiled quotient kernels (stark_jit.hip) ----
+static GlError stark_compile_all(const std::vector<Stark *> &tables, void *ctx) {
+    {  // the context's device becomes current: the modules are loaded there
+        const plonky2_hip::NttTables *tb;
+        TRY(tables_of(ctx, &tb));
+    }
+    std::vector<Stark *> todo;
+    for (Stark *s : tables)
+        if (!s->jit) todo.push_back(s);
+    if (todo.empty()) return ok();  // a second call is a no-op
+    std::vector<std::string> sources;
+    for (Stark *s : todo) sources.push_back(plonky2_hip::stark_jit_source(s->host));
+    std::vector<std::vector<char>> codes;
+    std::string err;
+    if (!plonky2_hip::stark_jit_compile_sources(sources, &codes, nullptr, &err)) return fail(GL_E_INVALID, err);
+    // all or nothing: a handle whose compile failed stays interpreted
+    std::vector<plonky2_hip::StarkJitKernel *> kernels;
+    for (size_t i = 0; i < todo.size(); i++) {
+        plonky2_hip::StarkJitKernel *k = plonky2_hip::stark_jit_load(todo[i]->host, sources[i], std::move(codes[i]), &err);
+        if (!k) {
+            for (plonky2_hip::StarkJitKernel *done : kernels) plonky2_hip::stark_jit_destroy(done);
+            return fail(GL_E_INVALID, err);
+        }
+        kernels.push_back(k);
+    }
+    for (size_t i = 0; i < todo.size(); i++) todo[i]->jit = kernels[i];
+    return ok();
+}
+
+static GlError stark_precompile_all(const std::vector<plonky2_hip::StarkJitDesc> &descs) {
+    if (plonky2_hip::jit_cache_dir().empty())
+        return fail(GL_E_INVALID, "no kernel cache to compile into: set PLONKY2_HIP_KERNEL_CACHE or create the directory kernel_cache next to the library");
+    std::vector<std::string> sources;
+    for (const plonky2_hip::StarkJitDesc &h : descs) sources.push_back(plonky2_hip::stark_jit_source(h));
+    std::vector<std::vector<char>> codes;
+    std::string err;
+    if (!plonky2_hip::stark_jit_compile_sources(sources, &codes, nullptr, &err)) return fail(GL_E_INVALID, err);
+    return ok();
+}
+
+GlError gl_stark_compile(void *stark, void *ctx) {
+    if (!stark || !ctx) return fail(GL_E_INVALID, "null pointer");
+    return stark_compile_all({static_cast<Stark *>(stark)}, ctx);
+}
+
+GlError gl_stark_tables_compile(void *tables, void *ctx) {
+    if (!tables || !ctx) return fail(GL_E_INVALID, "null pointer");
+    return stark_compile_all(static_cast<StarkTables *>(tables)->tables, ctx);
+}
+
+int gl_stark_is_compiled(const void *stark) { return stark && static_cast<const Stark *>(stark)->jit ? 1 : 0; }
+
+int gl_stark_tables_is_compiled(const void *tables) {
+    if (!tables) return 0;
+    for (const Stark *s : static_cast<const StarkTables *>(tables)->tables)
+        if (!s->jit) return 0;
+    return 1;
+}
+
+const char *gl_stark_kernel_source(const void *stark) {
+    const Stark *s = static_cast<const Stark *>(stark);
+    return s && s->jit ? plonky2_hip::stark_jit_kernel_source(s->jit) : nullptr;
+}
+
+const char *gl_stark_tables_kernel_source(const void *tables, uint32_t table) {
+    const StarkTables *T = static_cast<const StarkTables *>(tables);
+    if (!T || table >= T->tables.size()) return nullptr;
+    return gl_stark_kernel_source(T->tables[table]);
+}
+
+GlError gl_stark_precompile(uint32_t hasher, const GlStarkDesc *d) {
+    if (!d) return fail(GL_E_INVALID, "null pointer");
+    TRY(stark_check(hasher, d, 0));
+    return stark_precompile_all({stark_host_desc(d)});
+}
+
+GlError gl_stark_tables_precompile(uint32_t hasher, const GlStarkTablesDesc *d) {
+    if (!d) return fail(GL_E_INVALID, "null pointer");
+    std::vector<std::vector<uint32_t>> zs;
+    TRY(stark_tables_check(hasher, d, &zs));
+    std::vector<plonky2_hip::StarkJitDesc> descs;
+    for (uint32_t k = 0; k < d->num_tables; k++) {
+        descs.push_back(stark_host_desc(&d->tables[k]));
+        stark_host_ctl(&descs.back(), d, zs[k]);
+    }
+    return stark_precompile_all(descs);
 }
 
 }  // extern "C"

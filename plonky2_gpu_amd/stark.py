@@ -121,15 +121,33 @@ def _c_stark_desc(desc):
 
 
 class NativeStark:
-    """gl_stark_create: the handle of one STARK on one device; prove_bytes() = gl_stark_prove."""
+    """gl_stark_create: the handle of one STARK on one device; prove_bytes() = gl_stark_prove. `compiled`: compile() at once."""
 
-    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON):
+    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, compiled=False):
         self.ctx, self.desc, self.hasher = ctx, desc, _lib.hasher_id(hasher)
         self.ptr = None
         d, _keep = _c_stark_desc(desc)
         h = ctypes.c_void_p()
         _lib.call("gl_stark_create", self.hasher, ctypes.byref(d), ctypes.byref(h), ctx.ptr)
         self.ptr = h.value
+        if compiled:
+            self.compile()
+
+    def compile(self):
+        """gl_stark_compile: from now on the quotient runs the kernel generated from this STARK's description instead of the
+        interpreter — the same values. Only between proofs; a second call is a no-op; on failure (Plonky2HipError with the
+        compiler's log) the handle stays interpreted and usable."""
+        _lib.call("gl_stark_compile", self.ptr, self.ctx.ptr)
+
+    @property
+    def is_compiled(self):
+        return bool(_lib.load().gl_stark_is_compiled(self.ptr))
+
+    @property
+    def kernel_source(self):
+        """the generated HIP source, or None unless compiled"""
+        src = _lib.load().gl_stark_kernel_source(self.ptr)
+        return None if src is None else src.decode()
 
     def prove_bytes(self, trace, public_inputs, timing=None, ctx=None):
         """`trace`: host [num_columns][n] value columns or a DeviceBuffer; `ctx`: another context of the handle's device (several host
@@ -436,15 +454,33 @@ def _tables_c_desc(desc, flat):
 
 class NativeStarkTables:
     """gl_stark_tables_create: the handle of several STARKs and their cross-table lookups on one device. `flat`: the arrays of
-    desc.flatten(), for callers that build them themselves."""
+    desc.flatten(), for callers that build them themselves. `compiled`: compile() at once."""
 
-    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, flat=None):
+    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, flat=None, compiled=False):
         self.ctx, self.desc, self.hasher = ctx, desc, _lib.hasher_id(hasher)
         self.ptr = None
         d, _keep = _tables_c_desc(desc, flat if flat is not None else desc.flatten())
         h = ctypes.c_void_p()
         _lib.call("gl_stark_tables_create", self.hasher, ctypes.byref(d), ctypes.byref(h), ctx.ptr)
         self.ptr = h.value
+        if compiled:
+            self.compile()
+
+    def compile(self):
+        """gl_stark_tables_compile: one generated quotient kernel per table (program, permutation checks and the table's CTL
+        checks), as NativeStark.compile; all tables or none."""
+        _lib.call("gl_stark_tables_compile", self.ptr, self.ctx.ptr)
+
+    @property
+    def is_compiled(self):
+        return bool(_lib.load().gl_stark_tables_is_compiled(self.ptr))
+
+    @property
+    def kernel_source(self):
+        """the generated HIP source per table, or None unless compiled"""
+        if not self.is_compiled:
+            return None
+        return [_lib.load().gl_stark_tables_kernel_source(self.ptr, k).decode() for k in range(len(self.desc.tables))]
 
     def prove_bytes(self, traces, timing=None, ctx=None):
         """`traces`: per table host [num_columns][n] value columns or a DeviceBuffer; `timing`: a list that receives one dict of stage
@@ -506,6 +542,18 @@ class NativeStarkTables:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def precompile(desc, hasher=_lib.GL_HASHER_POSEIDON):
+    """gl_stark_precompile / gl_stark_tables_precompile of a StarkDesc / StarkTablesDesc: validate as the handle's constructor
+    does, generate the quotient kernel(s) and compile them into the kernel cache. Needs no device: what a build machine runs so
+    that compile() finds its kernels."""
+    if isinstance(desc, StarkTablesDesc):
+        d, _keep = _tables_c_desc(desc, desc.flatten())
+        _lib.call("gl_stark_tables_precompile", _lib.hasher_id(hasher), ctypes.byref(d))
+    else:
+        d, _keep = _c_stark_desc(desc)
+        _lib.call("gl_stark_precompile", _lib.hasher_id(hasher), ctypes.byref(d))
 
 
 # ---------------------------------------------------------------- wire format (include/plonky2_hip.h, gl_stark_tables_prove)

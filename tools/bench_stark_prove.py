@@ -18,11 +18,28 @@ tables of 100, 30 and 8 columns at 2^18, 2^16 and 2^14 rows, degree 3, tied by f
 standard_fast_config at its own size. In the same run the three tables are also proved one by one with gl_stark_prove, without their
 lookups; the result — per-table stage times, both totals and their ratio — goes to --ctl-out (profiles/stark_ctl_prove.json).
 
-  python tools/bench_stark_prove.py --shapes ctl [--reps 7] [--ctl-out profiles/stark_ctl_prove.json]"""
+  python tools/bench_stark_prove.py --shapes ctl [--reps 7] [--ctl-out profiles/stark_ctl_prove.json]
+
+--compiled measures the compiled quotient kernels (gl_stark_compile, csrc/stark_jit.hip) against the interpreter IN THE SAME RUN:
+for every shape and size the same trace is proved through an interpreted and a compiled handle, the bytes must be equal (else the
+tool exits non-zero), and median / min / max and stage_ms of both are recorded, with compile_ms cold (an empty temporary
+PLONKY2_HIP_KERNEL_CACHE; the compiler's own library is asked not to cache either, AMD_COMGR_CACHE=0) and warm (the same cache
+again). A shape's source does not depend on the number of rows: the FIRST size of a shape carries the cold figure, the later ones
+come back from the compiler library in about 11 ms. The shapes are fibonacci, wide, ctl and
+
+  dense      100 columns, degree 3, 1 466 instructions at the density of the reference's bitwise tables: a filter column, 96 bit
+             columns (three words of 32 bits) and three word columns; per bit column booleanity and the xor of two neighbours
+             against the next row, per word the 32-bit recomposition by ACC / ACCR, every constraint under the filter. Timed
+             through gl_stark_quotient_polys on random words (that needs no valid trace), compiled against interpreted.
+
+  python tools/bench_stark_prove.py --compiled [--shapes fibonacci,wide,dense,ctl] [--reps 7] [--compiled-out profiles/stark_compiled.json]"""
 import argparse
+import ctypes
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,10 +173,10 @@ def ctl_table(ctx, columns, degree_bits, flags):
     return a.program(), d_trace, 1 + 3 * triples
 
 
-def measure_ctl(ctx, reps, hasher="poseidon"):
-    """Four lookups, all of them satisfied: the first 2^14 counters of tables 0 and 1 into table 2 and the first 2^16 counters of
-    table 0 into table 1 (filtered on the looking side by a flag column, on the looked side by the constant 1), and table 2 into
-    itself without filters over two columns: 4, 4 and 8 CTL Zs."""
+def ctl_system(ctx, hasher="poseidon"):
+    """(StarkTablesDesc, the tables' StarkDescs, traces in HBM). Four lookups, all of them satisfied: the first 2^14 counters of
+    tables 0 and 1 into table 2 and the first 2^16 counters of table 0 into table 1 (filtered on the looking side by a flag column,
+    on the looked side by the constant 1), and table 2 into itself without filters over two columns: 4, 4 and 8 CTL Zs."""
     Col, Twc, Lookup = pstark.CtlColumn, pstark.TableWithColumns, pstark.CrossTableLookup
     flags = ((14, 16), (14,), ())
     built = [ctl_table(ctx, cols, db, fl) for (cols, db), fl in zip(CTL_TABLES, flags)]
@@ -172,7 +189,11 @@ def measure_ctl(ctx, reps, hasher="poseidon"):
                Lookup([Twc(0, counter, Col.single(f0 + 1))], Twc(1, counter, one)), Lookup([Twc(2, both)], Twc(2, both))]
     desc = pstark.StarkTablesDesc(descs, lookups)
     desc.validate(hasher)
-    traces = [d for _, d, _ in built]
+    return desc, descs, [d for _, d, _ in built]
+
+
+def measure_ctl(ctx, reps, hasher="poseidon"):
+    desc, descs, traces = ctl_system(ctx, hasher)
 
     def timed(fn):
         first = fn()
@@ -213,20 +234,201 @@ def measure_ctl(ctx, reps, hasher="poseidon"):
     return res
 
 
+# ---------------------------------------------------------------- --compiled: the compiled quotient kernels against the interpreter
+DENSE_WORDS = 3
+
+
+def dense_desc(degree_bits):
+    """the description of `dense`: column 0 the filter, columns 1 .. 96 bits, columns 97 .. 99 words"""
+    bits, cols = 32 * DENSE_WORDS, 1 + 33 * DENSE_WORDS
+    a = pstark.StarkAsm()
+    f, one = a.local(0), a.imm(1)
+    for w in range(DENSE_WORDS):
+        halves = []
+        for h in range(2):  # 16 bits per ACCR: 32 weights up to 2^31 would pass the accumulator's bound of 2^63
+            for k in range(16):
+                j = 32 * w + 16 * h + k
+                b = a.local(1 + j)
+                a.acc(b, 1 << k)
+                t = a.sub(b, one)
+                a.mul(b, t, dst=t)
+                a.mul(f, t, dst=t)
+                a.emit(t)  # f b (b - 1)
+                b2, nxt = a.local(1 + (j + 1) % bits), a.next(1 + j)
+                a.mul(b, b2, dst=t)
+                a.add(b, b2, dst=b)
+                a.mulk(t, 1, dst=t)
+                a.sub(b, t, dst=b)  # b xor b' = b + b' - 2 b b'
+                a.sub(nxt, b, dst=nxt)
+                a.mul(f, nxt, dst=nxt)
+                a.emit_transition(nxt)  # f (b_j' - (b_j xor b_j+1))
+                a.free(b, t, b2, nxt)
+            halves.append(a.accr())
+        lo, s = halves
+        a.mulk(s, 16, dst=s)
+        a.add(lo, s, dst=s)
+        word = a.local(1 + bits + w)
+        a.sub(word, s, dst=s)
+        a.mul(f, s, dst=s)
+        a.emit(s)  # f (word - sum 2^k b_k)
+        a.free(lo, word, s)
+    instrs, imms = a.program()
+    return pstark.StarkDesc(degree_bits, cols, 0, 3, 2, fast_config_fri_params(degree_bits), instrs, imms, [])
+
+
+def _stats(ms):
+    return {"median_ms": round(float(np.median(ms)), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+
+def _compile_ms(make_handle):
+    """(cold, warm): gl_stark_compile / gl_stark_tables_compile of a fresh handle with an empty temporary kernel cache, and of
+    another fresh handle with the cache the first one filled"""
+    cache = tempfile.mkdtemp(prefix="stark_kernel_cache_")
+    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
+    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
+    try:
+        out = []
+        for _ in range(2):
+            h = make_handle()
+            t0 = time.perf_counter()
+            h.compile()
+            out.append(round((time.perf_counter() - t0) * 1e3, 1))
+            h.close()
+        return out
+    finally:
+        if saved is None:
+            os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
+        else:
+            os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
+        shutil.rmtree(cache, ignore_errors=True)
+
+
+def _both(reps, interpreted, compiled):
+    """`reps` timed calls of each, alternating, after two warm-up calls of each; both must return what the interpreter returned first"""
+    first = interpreted()
+    if compiled() != first:
+        raise SystemExit("bench_stark_prove: the compiled handle's bytes differ from the interpreted handle's")
+    interpreted(), compiled()
+    ms = ([], [])
+    for _ in range(reps):
+        for k, fn in enumerate((interpreted, compiled)):
+            t0 = time.perf_counter()
+            data = fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+            if data != first:
+                raise SystemExit("bench_stark_prove: the bytes changed between two calls")
+    return _stats(ms[0]), _stats(ms[1])
+
+
+def measure_compiled(ctx, make, degree_bits, reps, hasher="poseidon"):
+    desc, d_trace, pis = make(ctx, degree_bits)
+    cold, warm = _compile_ms(lambda: pg.NativeStark(ctx, desc, hasher))
+    handles = [pg.NativeStark(ctx, desc, hasher), pg.NativeStark(ctx, desc, hasher, compiled=True)]
+    res = {"columns": desc.num_columns, "instructions": int(desc.instrs.shape[0]), "compile_ms": {"cold": cold, "warm": warm}}
+    res["interpreted"], res["compiled"] = _both(reps, *[lambda ns=ns: ns.prove_bytes(d_trace, pis) for ns in handles])
+    for key, ns in zip(("interpreted", "compiled"), handles):
+        timing = {}
+        ns.prove_bytes(d_trace, pis, timing)
+        res[key]["stage_ms"] = {k: round(v, 3) for k, v in timing.items()}
+        ns.close()
+    d_trace.free()
+    return res
+
+
+def measure_dense(ctx, degree_bits, reps, hasher="poseidon"):
+    """gl_stark_quotient_polys on random words in place of the trace's LDE: the call ends synchronised and includes the upload of the
+    (empty) public inputs and the coset iNTT of the two quotient columns, the same on both sides"""
+    desc = dense_desc(degree_bits)
+    n_ext, size = 1 << (degree_bits + 1), 1 << (degree_bits + desc.quotient_degree_bits)
+    rng = np.random.default_rng(degree_bits)
+    d_lde = pg.DeviceBuffer(ctx, desc.num_columns * n_ext)
+    for c in range(desc.num_columns):
+        _lib.call("gl_memcpy_h2d", d_lde.at(c * n_ext), rng.integers(0, P, size=n_ext, dtype=np.uint64), 8 * n_ext, ctx.ptr)
+    alphas = np.ascontiguousarray(rng.integers(0, P, size=2, dtype=np.uint64))
+    pis = np.zeros(1, dtype=np.uint64)
+    cold, warm = _compile_ms(lambda: pg.NativeStark(ctx, desc, hasher))
+    handles = [pg.NativeStark(ctx, desc, hasher), pg.NativeStark(ctx, desc, hasher, compiled=True)]
+    outs = [pg.DeviceBuffer(ctx, 2 * size) for _ in handles]
+
+    def call(ns, d_q):
+        _lib.call("gl_stark_quotient_polys", ns.ptr, d_lde.ptr, None, n_ext, alphas, None, pis, d_q.ptr, ctx.ptr)
+
+    for ns, d_q in zip(handles, outs):
+        call(ns, d_q)
+    if not (outs[0].download() == outs[1].download()).all():
+        raise SystemExit("bench_stark_prove: the compiled handle's quotient differs from the interpreted handle's")
+    ms = ([], [])
+    for _ in range(reps):
+        for k, (ns, d_q) in enumerate(zip(handles, outs)):
+            t0 = time.perf_counter()
+            call(ns, d_q)
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    for ns in handles:
+        ns.close()
+    for b in outs + [d_lde]:
+        b.free()
+    return {"columns": desc.num_columns, "instructions": int(desc.instrs.shape[0]), "compile_ms": {"cold": cold, "warm": warm},
+            "interpreted": dict(_stats(ms[0]), call="gl_stark_quotient_polys"), "compiled": dict(_stats(ms[1]), call="gl_stark_quotient_polys")}
+
+
+def measure_ctl_compiled(ctx, reps, hasher="poseidon"):
+    desc, _, traces = ctl_system(ctx, hasher)
+    cold, warm = _compile_ms(lambda: pg.NativeStarkTables(ctx, desc, hasher))
+    handles = [pg.NativeStarkTables(ctx, desc, hasher), pg.NativeStarkTables(ctx, desc, hasher, compiled=True)]
+    res = {"tables": [{"columns": cols, "degree_bits": db, "ctl_zs": desc.num_ctl_zs(k), "instructions": int(desc.tables[k].instrs.shape[0])}
+                      for k, (cols, db) in enumerate(CTL_TABLES)], "compile_ms": {"cold": cold, "warm": warm}}
+    res["interpreted"], res["compiled"] = _both(reps, *[lambda nt=nt: nt.prove_bytes(traces) for nt in handles])
+    for key, nt in zip(("interpreted", "compiled"), handles):
+        timing = []
+        nt.prove_bytes(traces, timing=timing)
+        res[key]["stage_ms"] = [{s: round(v, 3) for s, v in t.items()} for t in timing]
+        res[key]["quotient_polys_ms"] = round(sum(t["quotient polys"] for t in timing), 3)
+        nt.close()
+    for d_trace in traces:
+        d_trace.free()
+    return res
+
+
+def main_compiled(a, ctx, res):
+    os.environ["AMD_COMGR_CACHE"] = "0"  # a cold compile_ms is meant to be hiprtc's own time (see the module's text on later sizes)
+    res = dict(res, yardstick="the interpreter (stark_quotient_values_kernel) in the same run: calls of the two handles alternate")
+    makers = {"fibonacci": fibonacci, "wide": wide}
+    for shape in a.shapes.split(","):
+        if shape == "ctl":
+            res["ctl"] = measure_ctl_compiled(ctx, a.reps)
+            continue
+        res[shape] = {}
+        for bits in range(a.min_bits, a.max_bits + 1):
+            res[shape]["2^%d" % bits] = measure_dense(ctx, bits, a.reps) if shape == "dense" else measure_compiled(ctx, makers[shape], bits, a.reps)
+            print(shape, bits, json.dumps(res[shape]["2^%d" % bits]), file=sys.stderr, flush=True)
+    ctx.close()
+    line = json.dumps(res)
+    if a.compiled_out:
+        os.makedirs(os.path.dirname(a.compiled_out), exist_ok=True)
+        with open(a.compiled_out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--min-bits", type=int, default=16)
     ap.add_argument("--max-bits", type=int, default=20)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--shapes", default="fibonacci,wide")
+    ap.add_argument("--shapes", default=None, help="default: fibonacci,wide; with --compiled: fibonacci,wide,dense,ctl")
+    ap.add_argument("--compiled", action="store_true", help="compiled quotient kernels against the interpreter, in one run")
+    ap.add_argument("--compiled-out", default=os.path.join(ROOT, "profiles", "stark_compiled.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stark_prove.json"))
     ap.add_argument("--ctl-out", default=os.path.join(ROOT, "profiles", "stark_ctl_prove.json"))
     a = ap.parse_args()
     if a.reps < 1 or not 6 <= a.min_bits <= a.max_bits <= 22:
         ap.error("--reps >= 1 and 6 <= --min-bits <= --max-bits <= 22")
+    a.shapes = a.shapes or ("fibonacci,wide,dense,ctl" if a.compiled else "fibonacci,wide")
     ctx = pg.Context(0)
     res = {"tool": "tools/bench_stark_prove.py", "library": _lib.load().gl_version().decode(), "hasher": "poseidon", "reps": a.reps,
            "config": "standard_fast_config: 2 challenges, rate_bits 1, cap_height 4, 16 PoW bits, arity 4 down to 2^5, 84 queries; trace resident"}
+    if a.compiled:
+        return main_compiled(a, ctx, res)
     makers = {"fibonacci": fibonacci, "wide": wide}
     shapes = a.shapes.split(",")
     if "ctl" in shapes:
