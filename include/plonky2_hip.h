@@ -775,6 +775,36 @@ GlError gl_stark_fill_lookups(uint64_t *d_trace, uint64_t trace_stride, uint64_t
                               uint32_t num_lookups, void *d_scratch, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The Keccak-f table: the reference's KeccakStark (evm/src/keccak/: keccak_stark.rs, columns.rs, round_flags.rs, logic.rs,
+ * constants.rs), the widest table of its multi-table prover — 2430 columns, 24 rows per permutation — with its trace built in
+ * HBM and its constraints emitted natively, so that gl_stark_prove / gl_stark_tables_prove prove it without the trace ever
+ * visiting the host.
+ * gl_keccak_table_trace = generate_trace_rows (keccak_stark.rs:53-72). d_inputs: [num_inputs][25] words of 64 bits in device
+ * memory, the Keccak-f[1600] states in the reference's order input[y * 5 + x]. d_trace receives [2430][pitch trace_stride] value
+ * columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. CONTRACT: rows 24 k .. 24 k + 23 are permutation k exactly
+ * as generate_trace_rows_for_perm fills them; the rows from 24 num_inputs up to n are the permutation of the all-zero state,
+ * repeated and cut off at n (pad_rows, then drain: a power of two is never a multiple of 24, so the last padding permutation is
+ * always cut). Every word written is canonical — a bit, a 32-bit limb or a round flag —, and every one of the 2430 columns is
+ * written on every row: the buffer need not be zeroed; the words between n and trace_stride are left untouched. Column indices
+ * are those of columns.rs (reg_b is an alias into A' and has no columns of its own). The call runs on ctx->stream, returns
+ * without waiting and allocates nothing. Refused with GL_E_INVALID and a message before anything is launched: degree_bits 0 or
+ * above 24, 24 * num_inputs > n, trace_stride < n, a NULL pointer (num_inputs == 0 is allowed and gives an all-padding trace;
+ * d_inputs may then be NULL), d_trace overlapping d_inputs.
+ * gl_keccak_table_program = eval_packed_generic (keccak_stark.rs:230-375) with eval_round_flags as ONE STARK program in the
+ * encoding of GlStarkDesc.h_instrs: 842 constraints of degree 3 in the reference's order (the order decides the powers of alpha
+ * and so the proof's bytes), the bit recompositions through ACC in blocks that keep its overflow contract, rc_value_bit folded in
+ * at emission. Device-free. It fills instrs, immediates and their counts; gates is NULL and num_gates 0; num_gate_constraints is
+ * the number of emitted constraints; release the result with gl_gate_programs_free. The table has no public inputs and no
+ * permutation pairs; its cross-table lookup (keccak_stark.rs:34-43) has the 50 input limbs then the 50 output limbs as columns —
+ * single columns 24 + 2 (5 x + y) + limb for input[5 y + x], and 2314 + 2 (5 x + y) + limb for output[5 y + x] except lane (0, 0),
+ * whose output limbs are columns 2428 and 2429 — and column 23 (the flag of the last round) as filter.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_KECCAK_TABLE_COLUMNS 2430
+GlError gl_keccak_table_trace(const uint64_t *d_inputs, uint64_t num_inputs, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                              void *ctx);
+GlError gl_keccak_table_program(GlGatePrograms *out);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

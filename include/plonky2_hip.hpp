@@ -404,4 +404,27 @@ inline void fill_lookups(const Context &ctx, uint64_t *d_trace, uint64_t trace_s
                                 d_scratch, ctx.get()));
 }
 
+// The Keccak-f table (plonky2_hip.h "The Keccak-f table"). keccak_table_trace: d_inputs [num_inputs][25] states -> d_trace
+// [2430][trace_stride] with 2^degree_bits rows, on the context's stream. keccak_table_program: its constraints; the instructions
+// and immediates are what GlStarkDesc.h_instrs / h_immediates take (constraint_degree 3, no public inputs, no pairs).
+inline void keccak_table_trace(const Context &ctx, const uint64_t *d_inputs, uint64_t num_inputs, uint32_t degree_bits, uint64_t *d_trace,
+                               uint64_t trace_stride) {
+    check(gl_keccak_table_trace(d_inputs, num_inputs, degree_bits, d_trace, trace_stride, ctx.get()));
+}
+struct KeccakTableProgram {
+    std::vector<GlGateInstr> instrs;
+    std::vector<uint64_t> immediates;
+    uint32_t num_constraints = 0;
+};
+inline KeccakTableProgram keccak_table_program() {
+    GlGatePrograms p;
+    check(gl_keccak_table_program(&p));
+    KeccakTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 }  // namespace plonky2_hip

@@ -155,6 +155,7 @@ class GlStarkTablesDesc(ctypes.Structure):
 
 
 GL_CTL_NO_FILTER = 0xFFFFFFFF
+GL_KECCAK_TABLE_COLUMNS = 2430
 GL_CHALLENGER_RESET, GL_CHALLENGER_HASH, GL_CHALLENGER_COMPACT = 1, 2, 4
 GL_PROVE_STAGES = 11
 GL_STARK_STAGES = 11
@@ -260,6 +261,8 @@ SIGNATURES = {
     "gl_sort_canonical": (GlError, [_vp, _vp, _u64, _vp, _vp]),
     "gl_lookup_permuted_cols": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "gl_stark_fill_lookups": (GlError, [_vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp]),
+    "gl_keccak_table_trace": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp]),
+    "gl_keccak_table_program": (GlError, [_vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

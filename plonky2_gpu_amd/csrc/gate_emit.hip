@@ -929,7 +929,241 @@ GlError emit_error(const std::string &msg) {
     return e;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's Keccak-f table (evm/src/keccak/keccak_stark.rs:230-375 with round_flags.rs:12-27 and
+// logic.rs) as ONE STARK program: plonky2_gpu_amd/keccak_table.py program(), call for call (tests/test_keccak_table_ref.py holds
+// the two against each other word for word).
+namespace keccak_table {
+
+enum : uint16_t { LOAD_NEXT = 11, EMIT_TRANSITION = 12, EMIT_FIRST_ROW = 13 };
+constexpr int NUM_ROUNDS = 24;
+const uint64_t RC[NUM_ROUNDS] = {
+    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull, 0x000000000000808Bull, 0x0000000080000001ull,
+    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008Aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000Aull,
+    0x000000008000808Bull, 0x800000000000008Bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
+    0x000000000000800Aull, 0x800000008000000Aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+const int R[5][5] = {{0, 36, 3, 41, 18}, {1, 44, 10, 45, 2}, {62, 6, 43, 15, 61}, {28, 55, 25, 21, 56}, {27, 20, 39, 8, 14}};
+
+// columns.rs
+int reg_step(int i) { return i; }
+int reg_a(int x, int y) { return 24 + (x * 5 + y) * 2; }
+int reg_c(int x, int z) { return 74 + x * 64 + z; }
+int reg_c_prime(int x, int z) { return 394 + x * 64 + z; }
+int reg_a_prime(int x, int y, int z) { return 714 + x * 64 * 5 + y * 64 + z; }
+int reg_b(int x, int y, int z) {
+    const int a = (x + 3 * y) % 5;
+    return reg_a_prime(a, x, (z + 64 - R[a][x]) % 64);
+}
+int reg_a_prime_prime(int x, int y) { return 2314 + x * 2 * 5 + y * 2; }
+int reg_a_prime_prime_0_0_bit(int i) { return 2364 + i; }
+int reg_a_prime_prime_prime(int x, int y) { return x == 0 && y == 0 ? 2428 : reg_a_prime_prime(x, y); }
+
+struct Asm : GateAsm {
+    explicit Asm(ImmediatePool *p) : GateAsm(p) {}
+    int local(int i) { return op(LOAD_WIRE, i); }
+    int next(int i) { return op(LOAD_NEXT, i); }
+    void emit_transition(int a) { instrs.push_back(GlGateInstr{EMIT_TRANSITION, 0, field(a), 0}); }
+    void emit_first_row(int a) { instrs.push_back(GlGateInstr{EMIT_FIRST_ROW, 0, field(a), 0}); }
+    // xor_gen(x, y) = x + y - 2 x y in a fresh register; x and y stay
+    int xor2(int x, int y) {
+        const int s = add(x, y);
+        const int m = mul(x, y);
+        mulk(m, 1, m);
+        sub(s, m, s);
+        free1(m);
+        return s;
+    }
+    // xor3_gen(x, y, z) = xor_gen(x, xor_gen(y, z))
+    int xor3(int x, int y, int z) {
+        const int t = xor2(y, z);
+        const int u = xor2(x, t);
+        free1(t);
+        return u;
+    }
+    // sum_{k < 32} 2^k bit(z0 + k) in two blocks of 16 weights joined by a shift; bit(z) returns a register that is freed here
+    template <class Bit>
+    int limb(Bit bit, int z0) {
+        int halves[2];
+        for (int h = 0; h < 2; h++) {
+            for (int k = 0; k < 16; k++) {
+                const int t = bit(z0 + 16 * h + k);
+                acc(t, (u128)1 << k);
+                free1(t);
+            }
+            halves[h] = accr();
+        }
+        const int lo = halves[0], hi = halves[1];
+        mulk(hi, 16, hi);
+        add(hi, lo, hi);
+        free1(lo);
+        return hi;
+    }
+};
+
+Program program(ImmediatePool &pool) {
+    Asm a(&pool);
+    // eval_round_flags
+    {
+        const int s0 = a.local(reg_step(0));
+        const int one = a.imm(1);
+        a.emit_first_row(a.sub(s0, one));
+    }
+    for (int i = 1; i < NUM_ROUNDS; i++) {
+        a.release();
+        a.emit_first_row(a.local(reg_step(i)));
+    }
+    for (int i = 0; i < NUM_ROUNDS; i++) {
+        a.release();
+        const int nx = a.next(reg_step((i + 1) % NUM_ROUNDS));
+        const int lc = a.local(reg_step(i));
+        a.emit_transition(a.sub(nx, lc));
+    }
+    // C'[x, z] = xor(C[x, z], C[x - 1, z], C[x + 1, z - 1])
+    for (int x = 0; x < 5; x++)
+        for (int z = 0; z < 64; z++) {
+            a.release();
+            const int c0 = a.local(reg_c(x, z));
+            const int c1 = a.local(reg_c((x + 4) % 5, z));
+            const int c2 = a.local(reg_c((x + 1) % 5, (z + 63) % 64));
+            const int x3 = a.xor3(c0, c1, c2);
+            const int cp = a.local(reg_c_prime(x, z));
+            a.emit(a.sub(cp, x3));
+        }
+    // A[x, y, z] = xor(A'[x, y, z], C[x, z], C'[x, z]), recomposed into the two input limbs
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++) {
+            auto bit = [&](int z) {
+                const int ap = a.local(reg_a_prime(x, y, z));
+                const int c = a.local(reg_c(x, z));
+                const int cp = a.local(reg_c_prime(x, z));
+                const int t = a.xor3(ap, c, cp);
+                a.free({ap, c, cp});
+                return t;
+            };
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int computed = a.limb(bit, 32 * l);
+                const int al = a.local(reg_a(x, y) + l);
+                a.emit(a.sub(computed, al));
+            }
+        }
+    // diff (diff - 2) (diff - 4) = 0 with diff = sum_i A'[x, i, z] - C'[x, z]
+    for (int x = 0; x < 5; x++)
+        for (int z = 0; z < 64; z++) {
+            a.release();
+            const int s = a.local(reg_a_prime(x, 0, z));
+            for (int i = 1; i < 5; i++) {
+                const int t = a.local(reg_a_prime(x, i, z));
+                a.add(s, t, s);
+                a.free1(t);
+            }
+            const int cp = a.local(reg_c_prime(x, z));
+            const int diff = a.sub(s, cp);
+            const int two = a.imm(2);
+            const int d2 = a.sub(diff, two);
+            const int four = a.imm(4);
+            const int d4 = a.sub(diff, four);
+            const int m = a.mul(diff, d2);
+            a.emit(a.mul(m, d4));
+        }
+    // A''[x, y] = xor(B[x, y], andn(B[x + 1, y], B[x + 2, y]))
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++)
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int one = a.imm(1);
+                auto bit = [&](int z) {
+                    const int b0 = a.local(reg_b(x, y, z));
+                    const int b1 = a.local(reg_b((x + 1) % 5, y, z));
+                    const int b2 = a.local(reg_b((x + 2) % 5, y, z));
+                    const int n = a.sub(one, b1);
+                    a.mul(n, b2, n);  // andn_gen(x, y) = (1 - x) y
+                    const int t = a.xor2(b0, n);
+                    a.free({b0, b1, b2, n});
+                    return t;
+                };
+                const int computed = a.limb(bit, 32 * l);
+                const int app = a.local(reg_a_prime_prime(x, y) + l);
+                a.emit(a.sub(computed, app));
+            }
+    // A'''[0, 0] = A''[0, 0] xor RC: the bits of A''[0, 0] recompose into its limbs ...
+    for (int l = 0; l < 2; l++) {
+        a.release();
+        const int computed = a.limb([&](int z) { return a.local(reg_a_prime_prime_0_0_bit(z)); }, 32 * l);
+        const int app = a.local(reg_a_prime_prime(0, 0) + l);
+        a.emit(a.sub(computed, app));
+    }
+    // ... and xored with the round's constant into the limbs of A'''[0, 0]
+    auto xored_bit = [&](int i) {
+        const int b = a.local(reg_a_prime_prime_0_0_bit(i));
+        bool any = false;
+        for (int r = 0; r < NUM_ROUNDS; r++)
+            if ((RC[r] >> i) & 1) {
+                const int f = a.local(reg_step(r));
+                a.acc(f, 1, 1);
+                a.free1(f);
+                any = true;
+            }
+        if (!any) return b;
+        const int rc = a.accr(1);
+        const int t = a.xor2(b, rc);
+        a.free({b, rc});
+        return t;
+    };
+    for (int l = 0; l < 2; l++) {
+        a.release();
+        const int computed = a.limb(xored_bit, 32 * l);
+        const int appp = a.local(reg_a_prime_prime_prime(0, 0) + l);
+        a.emit(a.sub(computed, appp));
+    }
+    // this round's output is the next round's input, except behind the last round
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++)
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int one = a.imm(1);
+                const int last = a.local(reg_step(NUM_ROUNDS - 1));
+                const int not_last = a.sub(one, last);
+                const int out = a.local(reg_a_prime_prime_prime(x, y) + l);
+                const int in = a.next(reg_a(x, y) + l);
+                const int diff = a.sub(out, in);
+                a.emit_transition(a.mul(not_last, diff));
+            }
+    return a.instrs;
+}
+
+}  // namespace keccak_table
+
 }  // namespace
+
+extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) {
+    if (!out) return emit_error("gl_keccak_table_program: null pointer");
+    memset(out, 0, sizeof *out);
+    try {
+        ImmediatePool pool;
+        const Program prog = keccak_table::program(pool);
+        uint32_t emits = 0;
+        for (const GlGateInstr &in : prog) emits += in.op == EMIT || in.op >= keccak_table::EMIT_TRANSITION;
+        out->num_instrs = (uint32_t)prog.size();
+        out->num_immediates = (uint32_t)pool.values.size();
+        out->num_gate_constraints = emits;
+        out->instrs = (GlGateInstr *)malloc(prog.size() * sizeof(GlGateInstr));
+        out->immediates = (uint64_t *)malloc(pool.values.size() * sizeof(uint64_t));
+        if (!out->instrs || !out->immediates) {
+            gl_gate_programs_free(out);
+            return emit_error("gl_keccak_table_program: out of memory");
+        }
+        memcpy(out->instrs, prog.data(), prog.size() * sizeof(GlGateInstr));
+        memcpy(out->immediates, pool.values.data(), pool.values.size() * sizeof(uint64_t));
+    } catch (const std::exception &ex) {
+        gl_gate_programs_free(out);
+        return emit_error(std::string("gl_keccak_table_program: ") + ex.what());
+    }
+    GlError ok;
+    ok.code = 0;
+    ok.message = nullptr;
+    return ok;
+}
 
 extern "C" GlError gl_gate_programs_emit(const GlGateSpec *gates, uint32_t num_gates, const uint32_t *group_bounds, uint32_t num_selectors,
                                          GlGatePrograms *out) {
