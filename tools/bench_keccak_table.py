@@ -10,7 +10,8 @@ floor of its 2430 columns and against a host route, and whole interpreted proofs
   prove       gl_stark_prove of the device-built trace, interpreted, under starky's standard_fast_config, with its stage times
               (sizes --prove-bits, default 12 and 14)
 
-Oracle-free. One JSON line on stdout and in --out (default profiles/keccak_table.json).
+Oracle-free; the reference verifier accepts the proofs of `prove` at 2^12 and 2^14 rows in tests/test_gpu_stark_scale.py, which takes
+inputs_for and the parameters from here. One JSON line on stdout and in --out (default profiles/keccak_table.json).
 
   python tools/bench_keccak_table.py [--bits 14 16 18 20] [--prove-bits 12 14] [--reps 7] [--device LABEL] [--out FILE]"""
 import argparse

@@ -8,8 +8,9 @@ cap_height 4, 16 proof-of-work bits, ConstantArityBits(4, 5), 84 query rounds; s
 
 at 2^16 .. 2^20 rows, trace resident in HBM. Per shape and size: the handle is created and warmed (two proofs), then `--reps` proofs
 are timed by the wall clock around gl_stark_prove (it ends synchronised); median, min and max, and the h_stage_ms breakdown of one
-further proof. Oracle-free: every proof must equal the first one and round-trip through the wire format. One JSON line on stdout
-(and --out, by default profiles/stark_prove.json).
+further proof. Oracle-free: every proof must equal the first one and round-trip through the wire format; that the proofs of these
+shapes are VALID — accepted by the reference verifier — is tests/test_gpu_stark_scale.py's, which imports the shapes from here. One
+JSON line on stdout (and --out, by default profiles/stark_prove.json).
 
   python tools/bench_stark_prove.py [--min-bits 16] [--max-bits 20] [--reps 7] [--out profiles/stark_prove.json]
 
