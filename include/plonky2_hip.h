@@ -197,7 +197,11 @@ GlError gl_permutation_partial_products(const uint64_t *d_wires, uint64_t wires_
  *     this and refuses the program otherwise; the interpreter cannot (its program is in device memory), the
  *     emitters in plonky2_gpu_amd/gate_program.py enforce it when they generate code. Accumulators start at 0 in
  *     every gate.
- * (64 registers). Gate g is described by GlGateDesc {row = its index in the circuit's gate list,
+ * (64 registers). Indices are taken as written: a register index >= 64, an accumulator index >= 4 (ACC's dst, ACCR's a),
+ * a MULK shift >= 64 and a LOAD_PI index >= 4 are GL_E_INVALID wherever the host sees the programs — gl_gate_kernel_build,
+ * and gl_circuit_create for the compiled kernel and for the interpreter alike. (The device code masks them, & 63 and & 3,
+ * so that a GlGateProgram handed over in device memory cannot index out of bounds; no valid program relies on that.)
+ * A register is written before it is read. Gate g is described by GlGateDesc {row = its index in the circuit's gate list,
  * selector_index, group_start, group_end (selectors_info.groups[selector_index]), prog_start, prog_len}.
  * Constraint k of every gate accumulates into term k, multiplied by the gate's filter. */
 typedef struct GlGateInstr {

@@ -133,6 +133,18 @@ bool gate_programs_validate(const uint16_t *instrs, uint32_t num_instrs, const u
             const uint16_t op = instrs[4 * pc], dst = instrs[4 * pc + 1], a = instrs[4 * pc + 2], b = instrs[4 * pc + 3];
             const bool reads_a = op == GP_ADD || op == GP_SUB || op == GP_MUL || op == GP_EMIT || op == GP_MULK || op == GP_ACC;
             const bool reads_b = op == GP_ADD || op == GP_SUB || op == GP_MUL;
+            // Indices are taken as written: the interpreter and the generators mask them (& 63, & 3) for memory safety only, and a program
+            // that leaned on the masking would mean different things to them (the per-gate generator shifts a MULK by up to 95).
+            const bool writes = op != GP_EMIT && op != GP_ACC && op <= GP_ACCR;
+            const char *range = (reads_a && a >= MAX_REGS) || (reads_b && b >= MAX_REGS) || (writes && dst >= MAX_REGS) ? "register index >= 64"
+                                : (op == GP_ACC && dst >= 4) || (op == GP_ACCR && a >= 4)                              ? "accumulator index >= 4"
+                                : (op == GP_MULK && b >= 64)                                                           ? "MULK shift >= 64"
+                                : (op == GP_LOAD_PI && a >= 4)                                                         ? "LOAD_PI index >= 4"
+                                                                                                                       : nullptr;
+            if (range) {
+                *error = "gate " + std::to_string(g) + ": " + range + " (instruction " + std::to_string(pc - ps) + ")";
+                return false;
+            }
             if ((reads_a && !written[a & (MAX_REGS - 1)]) || (reads_b && !written[b & (MAX_REGS - 1)])) {
                 *error = "gate " + std::to_string(g) + ": register read before any write (instruction " + std::to_string(pc - ps) + ")";
                 return false;
@@ -401,7 +413,9 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
             case GP_ADD:
             case GP_SUB:
             case GP_MUL:
-                if (reg[ra] == ~0u || reg[rb] == ~0u) {
+                // (a rewritten range check's c = t * u reads u, the t + 2 that is not generated: when the program wrote u to a register
+                // nothing had written before, that register holds no node — the square takes t alone)
+                if (pp.kind == Peep::SQUARE ? reg[pp.src] == ~0u : (reg[ra] == ~0u || reg[rb] == ~0u)) {
                     *error = "register read before any write";
                     return false;
                 }

@@ -3,56 +3,20 @@ gate table is executed with Python integers — a direct reading of the opcode d
 including the two halves of an ACC accumulator and the bound both must respect — on random rows, and its
 constraints are compared with the oracle's restatement of the same gate (oracle/gates_ref.py, oracle/plonk_ref.py).
 The GPU suite runs the same programs through the interpreter and the run-time compiled kernel."""
+import os
 import random
+import sys
 
 import pytest
 
-from oracle import prove_ref
-from plonky2_gpu_amd import ed25519_circuit as ed
-from plonky2_gpu_amd import gate_program as gp
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from gate_exec import execute  # noqa: E402  (the executor, shared with tests/gate_fuzz.py)
+from oracle import prove_ref  # noqa: E402
+from plonky2_gpu_amd import ed25519_circuit as ed  # noqa: E402
+from plonky2_gpu_amd import gate_program as gp  # noqa: E402
 
 P = 0xFFFFFFFF00000001
-
-
-def execute(instrs, imms, num_selectors, consts, wires, pih):
-    """one gate's program on one row -> the list of emitted constraint values (mod p)"""
-    regs, out = {}, []
-    acc_lo, acc_hi = [0] * 4, [0] * 4
-    for op, dst, a, b in instrs:
-        if op == gp.LOAD_WIRE:
-            regs[dst] = wires[a]
-        elif op == gp.LOAD_CONST:
-            regs[dst] = consts[num_selectors + a]
-        elif op == gp.LOAD_PI:
-            regs[dst] = pih[a]
-        elif op == gp.LOAD_IMM:
-            regs[dst] = imms[a] % P
-        elif op == gp.ADD:
-            regs[dst] = (regs[a] + regs[b]) % P
-        elif op == gp.SUB:
-            regs[dst] = (regs[a] - regs[b]) % P
-        elif op == gp.MUL:
-            regs[dst] = regs[a] * regs[b] % P
-        elif op == gp.MULK:
-            regs[dst] = (regs[a] << b) % P
-        elif op == gp.EMIT:
-            out.append(regs[a])
-        elif op == gp.ACC:
-            # registers hold ANY u64 representative on the device: take the worst case for the bound, 2^32 - 1 per half
-            assert imms[b] < 1 << 32
-            x = regs[a]
-            acc_lo[dst] += (x & 0xFFFFFFFF) * imms[b]
-            acc_hi[dst] += (x >> 32) * imms[b]
-            execute.worst[dst] += 0xFFFFFFFF * imms[b]
-            assert execute.worst[dst] < 1 << 63, "an accumulator half could wrap"
-        elif op == gp.ACCR:
-            regs[dst] = (acc_lo[a] + (acc_hi[a] << 32)) % P
-            acc_lo[a] = acc_hi[a] = 0
-            execute.worst[a] = 0
-        else:
-            raise AssertionError("unknown opcode %d" % op)
-    assert acc_lo == [0] * 4 and acc_hi == [0] * 4, "an accumulator was left unreduced"
-    return out
 
 
 @pytest.mark.parametrize("row", range(len(ed.GATES)))
