@@ -809,6 +809,60 @@ GlError gl_keccak_table_trace(const uint64_t *d_inputs, uint64_t num_inputs, uin
 GlError gl_keccak_table_program(GlGatePrograms *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * The memory table: the reference's MemoryStark (evm/src/memory/: memory_stark.rs, columns.rs), the table whose height follows
+ * the length of the execution — 26 columns, one row per memory operation, dummy read or padding row — with its trace built in
+ * HBM from the UNSORTED operation list and its constraints emitted natively, so that gl_stark_prove / gl_stark_tables_prove
+ * prove it without the trace ever visiting the host.
+ * gl_memory_table_trace = generate_trace (memory_stark.rs:122-236), bit for bit. d_ops: [num_ops][14] words of 64 bits in device
+ * memory, one record per operation, exactly MemoryOp::into_row()[0..14]: FILTER, TIMESTAMP, IS_READ, ADDR_CONTEXT, ADDR_SEGMENT,
+ * ADDR_VIRTUAL, then the eight 32-bit limbs of the value, least significant first. Any order; the order of the list breaks the
+ * ties of equal (context, segment, virtual address, timestamp), as the reference's stable sorts do. LIMITS, checked on the
+ * device: FILTER and IS_READ are 0 or 1, every other word is below 2^32, 2 <= num_ops <= 2^30.
+ * d_trace receives [26][pitch trace_stride] value columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. CONTRACT:
+ * the rows are the reference's, quirks included — fill_gaps takes max_rc = next_power_of_two(num_ops) - 1 before any dummy is
+ * added, never looks at context or segment gaps, and pushes dummy reads of value 0 and filter 0 at virt + k (max_rc + 1) with
+ * timestamp 0 where the virtual address jumps and at timestamp + k max_rc where only the timestamp does; pad_memory_ops repeats
+ * the LAST ELEMENT OF THE VECTOR after fill_gaps (the last dummy pushed, else the largest operation) as a read with filter 0, so
+ * the padding rows can lie in the middle of the trace; then the first-change flags and RANGE_CHECK, COUNTER = 0 .. n, and
+ * RANGE_CHECK_PERMUTED / COUNTER_PERMUTED as permuted_cols gives them. Every word of the 26 columns is written on every row
+ * (columns 17 .. 21, between VIRTUAL_FIRST_CHANGE and RANGE_CHECK, as zeros; the last row's three flags and RANGE_CHECK are
+ * zero) and is canonical: the buffer need not be zeroed; the words between n and trace_stride are left untouched.
+ * The number of rows depends on the data: rows = num_ops + dummies, returned in *h_rows. With n = next_power_of_two(rows) the
+ * trace is the reference's; a larger degree_bits is allowed and gives more padding rows under the same max_rc. d_trace == NULL
+ * asks for the count alone (trace_stride is not read; degree_bits still sizes the scratch). PROTOCOL: the sort, the gaps, their
+ * prefix sums and every data refusal are decided on ctx->stream first; the host then reads rows and a status word — the call's
+ * ONE host wait —; the rows, the flags and the lookup columns are enqueued behind it and the call returns without waiting for
+ * them. Nothing is allocated: d_scratch is gl_memory_table_scratch_bytes(num_ops, degree_bits) bytes, 16-byte aligned (it
+ * includes what permuted_cols needs, about 8.7 max(n, num_ops) words) and holds nothing between calls; 0 is returned for
+ * arguments out of range.
+ * Refused with GL_E_INVALID and a message that names the reason, the trace untouched — for the data: rows > n (*h_rows still
+ * says what is needed); a word outside the limits above (*h_rows is 0); a context or segment gap whose range check would be >= n
+ * (the reference asserts there; not checked on a count-only call) — and before anything is launched: degree_bits outside 1 ..= 23
+ * (what gl_stark_create takes for constraints of degree 3), num_ops out of range, trace_stride < n, a NULL pointer other than
+ * d_trace, d_scratch not 16-byte aligned, d_ops, d_trace and d_scratch overlapping one another.
+ * gl_memory_table_program = eval_packed_generic (memory_stark.rs:242-319) as ONE STARK program in the encoding of
+ * GlStarkDesc.h_instrs, 23 constraints of degree 3 in the reference's order: the filter is boolean; a dummy row is a read; the
+ * four flags are boolean; the six transition constraints "no change before the flagged column"; the range check's transition
+ * constraint; the eight value constraints (plain constraints: they also bind the last row to row 0); eval_lookups of
+ * (RANGE_CHECK_PERMUTED, COUNTER_PERMUTED). Device-free; the result is laid out and released as gl_keccak_table_program's. The
+ * table has no public inputs; its permutation pairs are (RANGE_CHECK 22, RANGE_CHECK_PERMUTED 24) and (COUNTER 23,
+ * COUNTER_PERMUTED 25); its cross-table lookup (memory_stark.rs:29-39) has the 13 columns IS_READ 2, ADDR_CONTEXT 3,
+ * ADDR_SEGMENT 4, ADDR_VIRTUAL 5, the value limbs 6 .. 13, TIMESTAMP 1 and FILTER 0 as filter.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_MEMORY_TABLE_COLUMNS 26
+#define GL_MEMORY_TABLE_OP_WORDS 14
+uint64_t gl_memory_table_scratch_bytes(uint64_t num_ops, uint32_t degree_bits);
+GlError gl_memory_table_trace(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                              void *d_scratch, uint64_t *h_rows, void *ctx);
+GlError gl_memory_table_program(GlGatePrograms *out);
+/* Measurement hook: gl_memory_table_trace with an event between its stages. h_ms[5] receives the milliseconds of the sort, the
+ * gaps (dummy counts, their prefix sums, the decision), the rows, the flags and the lookup columns; the host's wait for the count
+ * lies between the second and the third and belongs to none. d_trace is required. Creates and destroys its events and waits for
+ * ctx->stream before it returns: not for use next to a proof in flight on the same context. */
+GlError gl_debug_memory_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                                       void *d_scratch, float *h_ms, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

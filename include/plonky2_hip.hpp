@@ -427,4 +427,27 @@ inline KeccakTableProgram keccak_table_program() {
     return out;
 }
 
+// The memory table (plonky2_hip.h "The memory table"). memory_table_trace: d_ops [num_ops][14] unsorted operations -> d_trace
+// [26][trace_stride] with 2^degree_bits rows; returns operations + dummies, which is all a call with d_trace == nullptr computes.
+// d_scratch: gl_memory_table_scratch_bytes(num_ops, degree_bits) bytes in HBM. The call waits once, for the count; the trace is
+// complete on the context's stream before a prove() of the same context reads it. memory_table_program: its constraints
+// (constraint_degree 3, no public inputs, pairs (22, 24) and (23, 25)).
+inline uint64_t memory_table_trace(const Context &ctx, const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                                   uint64_t trace_stride, void *d_scratch) {
+    uint64_t rows = 0;
+    check(gl_memory_table_trace(d_ops, num_ops, degree_bits, d_trace, trace_stride, d_scratch, &rows, ctx.get()));
+    return rows;
+}
+using MemoryTableProgram = KeccakTableProgram;  // instructions, immediates and the number of constraints
+inline MemoryTableProgram memory_table_program() {
+    GlGatePrograms p;
+    check(gl_memory_table_program(&p));
+    MemoryTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 }  // namespace plonky2_hip

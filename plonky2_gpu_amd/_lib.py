@@ -263,6 +263,10 @@ SIGNATURES = {
     "gl_stark_fill_lookups": (GlError, [_vp, _u64, _u64, _u32, _vp, _u32, _vp, _vp]),
     "gl_keccak_table_trace": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp]),
     "gl_keccak_table_program": (GlError, [_vp]),
+    "gl_memory_table_scratch_bytes": (_u64, [_u64, _u32]),
+    "gl_memory_table_trace": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(_u64), _vp]),
+    "gl_memory_table_program": (GlError, [_vp]),
+    "gl_debug_memory_table_stage_ms": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

@@ -1134,14 +1134,140 @@ Program program(ImmediatePool &pool) {
 
 }  // namespace keccak_table
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's memory table (evm/src/memory/memory_stark.rs:242-319 with lookup.rs:19-33) as ONE STARK
+// program: plonky2_gpu_amd/memory_table.py program(), call for call (tests/test_memory_table_ref.py holds the two against each
+// other word for word).
+namespace memory_table {
 
-extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) {
-    if (!out) return emit_error("gl_keccak_table_program: null pointer");
+enum : uint16_t { EMIT_LAST_ROW = 14 };
+// columns.rs
+enum {
+    FILTER = 0,
+    TIMESTAMP = 1,
+    IS_READ = 2,
+    ADDR_CONTEXT = 3,
+    ADDR_SEGMENT = 4,
+    ADDR_VIRTUAL = 5,
+    VALUE_START = 6,
+    CONTEXT_FIRST_CHANGE = 14,
+    SEGMENT_FIRST_CHANGE = 15,
+    VIRTUAL_FIRST_CHANGE = 16,
+    RANGE_CHECK = 22,
+    RANGE_CHECK_PERMUTED = 24,
+    COUNTER_PERMUTED = 25,
+};
+
+struct Asm : keccak_table::Asm {
+    explicit Asm(ImmediatePool *p) : keccak_table::Asm(p) {}
+    void emit_last_row(int a) { instrs.push_back(GlGateInstr{EMIT_LAST_ROW, 0, field(a), 0}); }
+    // eval_lookups (evm/src/lookup.rs:19-33), as StarkAsm.eval_lookups
+    void eval_lookups(int col_permuted_input, int col_permuted_table) {
+        const int local_perm_input = local(col_permuted_input);
+        const int next_perm_table = next(col_permuted_table);
+        const int next_perm_input = next(col_permuted_input);
+        const int diff_input_prev = sub(next_perm_input, local_perm_input);
+        const int diff_input_table = sub(next_perm_input, next_perm_table);
+        emit(mul(diff_input_prev, diff_input_table));
+        emit_last_row(diff_input_table);
+    }
+};
+
+Program program(ImmediatePool &pool) {
+    Asm a(&pool);
+    const int one = a.imm(1);
+    // the filter is 0 or 1
+    const int filter = a.local(FILTER);
+    {
+        const int t = a.sub(filter, one);
+        a.mul(filter, t, t);
+        a.emit(t);
+        a.free1(t);
+    }
+    // a dummy row (filter off) is a read
+    {
+        const int is_dummy = a.sub(one, filter);
+        const int is_read = a.local(IS_READ);
+        const int is_write = a.sub(one, is_read);
+        const int t = a.mul(is_dummy, is_write);
+        a.emit(t);
+        a.free({t, is_dummy, is_write, is_read, filter});
+    }
+    // first set of ordering constraints: the first_change flags and address_unchanged are boolean
+    const int context_first_change = a.local(CONTEXT_FIRST_CHANGE);
+    const int segment_first_change = a.local(SEGMENT_FIRST_CHANGE);
+    const int virtual_first_change = a.local(VIRTUAL_FIRST_CHANGE);
+    const int address_unchanged = a.sub(one, context_first_change);
+    a.sub(address_unchanged, segment_first_change, address_unchanged);
+    a.sub(address_unchanged, virtual_first_change, address_unchanged);
+    for (int flag : {context_first_change, segment_first_change, virtual_first_change, address_unchanged}) {
+        const int t = a.sub(one, flag);
+        a.mul(flag, t, t);
+        a.emit(t);
+        a.free1(t);
+    }
+    // second set: no change before the column of the flag that is set
+    int diffs[4];
+    const int diff_columns[4] = {ADDR_CONTEXT, ADDR_SEGMENT, ADDR_VIRTUAL, TIMESTAMP};
+    for (int k = 0; k < 4; k++) {
+        const int nxt = a.next(diff_columns[k]);
+        const int local = a.local(diff_columns[k]);
+        a.sub(nxt, local, nxt);
+        a.free1(local);
+        diffs[k] = nxt;
+    }
+    const int d_context = diffs[0], d_segment = diffs[1], d_virtual = diffs[2], d_timestamp = diffs[3];
+    const int transitions[6][2] = {{segment_first_change, d_context}, {virtual_first_change, d_context}, {virtual_first_change, d_segment},
+                                   {address_unchanged, d_context},    {address_unchanged, d_segment},    {address_unchanged, d_virtual}};
+    for (const auto &fd : transitions) {
+        const int t = a.mul(fd[0], fd[1]);
+        a.emit_transition(t);
+        a.free1(t);
+    }
+    // third set: the range check is the difference of the column that should be increasing
+    {
+        const int computed = a.sub(d_context, one);
+        a.mul(context_first_change, computed, computed);
+        const int terms[2][2] = {{segment_first_change, d_segment}, {virtual_first_change, d_virtual}};
+        for (const auto &fd : terms) {
+            const int t = a.sub(fd[1], one);
+            a.mul(fd[0], t, t);
+            a.add(computed, t, computed);
+            a.free1(t);
+        }
+        const int t = a.mul(address_unchanged, d_timestamp);
+        a.add(computed, t, computed);
+        a.free1(t);
+        const int range_check = a.local(RANGE_CHECK);
+        a.sub(range_check, computed, computed);
+        a.emit_transition(computed);
+        a.free({computed, range_check});
+    }
+    // the purportedly ordered log: a read of an unchanged address sees the value of the row before
+    const int gate = a.next(IS_READ);
+    a.mul(gate, address_unchanged, gate);
+    for (int i = 0; i < 8; i++) {
+        const int nxt = a.next(VALUE_START + i);
+        const int local = a.local(VALUE_START + i);
+        a.sub(nxt, local, nxt);
+        a.mul(gate, nxt, nxt);
+        a.emit(nxt);
+        a.free({nxt, local});
+    }
+    a.release();
+    a.eval_lookups(RANGE_CHECK_PERMUTED, COUNTER_PERMUTED);
+    return a.instrs;
+}
+
+}  // namespace memory_table
+
+// a table's STARK program as a GlGatePrograms without gate descriptors; num_gate_constraints counts its EMITs of every kind
+GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePool &), GlGatePrograms *out) {
+    if (!out) return emit_error(name + ": null pointer");
     memset(out, 0, sizeof *out);
     try {
         ImmediatePool pool;
-        const Program prog = keccak_table::program(pool);
+        const Program prog = build(pool);
         uint32_t emits = 0;
         for (const GlGateInstr &in : prog) emits += in.op == EMIT || in.op >= keccak_table::EMIT_TRANSITION;
         out->num_instrs = (uint32_t)prog.size();
@@ -1151,19 +1277,25 @@ extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) {
         out->immediates = (uint64_t *)malloc(pool.values.size() * sizeof(uint64_t));
         if (!out->instrs || !out->immediates) {
             gl_gate_programs_free(out);
-            return emit_error("gl_keccak_table_program: out of memory");
+            return emit_error(name + ": out of memory");
         }
         memcpy(out->instrs, prog.data(), prog.size() * sizeof(GlGateInstr));
         memcpy(out->immediates, pool.values.data(), pool.values.size() * sizeof(uint64_t));
     } catch (const std::exception &ex) {
         gl_gate_programs_free(out);
-        return emit_error(std::string("gl_keccak_table_program: ") + ex.what());
+        return emit_error(name + ": " + ex.what());
     }
     GlError ok;
     ok.code = 0;
     ok.message = nullptr;
     return ok;
 }
+
+}  // namespace
+
+extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) { return emit_table_program("gl_keccak_table_program", keccak_table::program, out); }
+
+extern "C" GlError gl_memory_table_program(GlGatePrograms *out) { return emit_table_program("gl_memory_table_program", memory_table::program, out); }
 
 extern "C" GlError gl_gate_programs_emit(const GlGateSpec *gates, uint32_t num_gates, const uint32_t *group_bounds, uint32_t num_selectors,
                                          GlGatePrograms *out) {

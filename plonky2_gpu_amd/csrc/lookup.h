@@ -36,4 +36,11 @@ hipError_t lookup_sort_canonical(const uint64_t *in, uint64_t *out, uint64_t n, 
 hipError_t lookup_permuted_cols(const uint64_t *inputs, const uint64_t *table, uint64_t n, uint64_t *permuted_inputs, uint64_t *permuted_table,
                                 const LookupScratch &s, hipStream_t stream);
 
+// The two pieces the memory table's trace generator (memory_table.hip) shares with permuted_cols. Both are enqueued on `stream`.
+// keys[0..n) sorted in place by their upper 32 bits alone, stably (the radix passes of digits 4 .. 7, uniform digits skipped):
+// with a position in the lower 32 bits this is one round of a multi-field sort. 1 <= n <= 2^31, `s` laid out for at least n / 2.
+hipError_t lookup_sort_by_upper_half(uint64_t *keys, uint64_t n, const LookupScratch &s, hipStream_t stream);
+// data[0..len) becomes its exclusive prefix sums; `totals` holds ceil(len / LOOKUP_SCAN_BLOCK) words.
+hipError_t lookup_exclusive_sums(uint64_t *data, uint64_t len, void *totals, hipStream_t stream);
+
 }  // namespace plonky2_hip

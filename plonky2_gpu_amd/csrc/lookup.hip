@@ -439,6 +439,14 @@ hipError_t lookup_sort_canonical(const uint64_t *in, uint64_t *out, uint64_t n, 
     return radix_sort(in, out, n, 1, 0, s, stream);
 }
 
+hipError_t lookup_sort_by_upper_half(uint64_t *keys, uint64_t n, const LookupScratch &s, hipStream_t stream) {
+    return radix_sort(keys, keys, n, 0, 4, s, stream);
+}
+
+hipError_t lookup_exclusive_sums(uint64_t *data, uint64_t len, void *totals, hipStream_t stream) {
+    return scan_in_place<AddU64, false>(data, len, totals, nullptr, stream);
+}
+
 hipError_t lookup_permuted_cols(const uint64_t *inputs, const uint64_t *table, uint64_t n, uint64_t *permuted_inputs, uint64_t *permuted_table,
                                 const LookupScratch &s, hipStream_t stream) {
     hipError_t e = radix_sort(inputs, permuted_inputs, n, 1, 0, s, stream);
