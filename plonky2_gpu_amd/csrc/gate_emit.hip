@@ -25,16 +25,18 @@
 #include <vector>
 
 #include "../../include/plonky2_hip.h"
+#include "gl_field.h"
+#include "program_isa.h"
 #define POSEIDON_CONST static const
 #include "poseidon_constants.h"
 
 namespace {
 
+using namespace plonky2_hip::isa;  // the opcodes, MAX_REGS, AccBound
+
 typedef unsigned __int128 u128;
-constexpr uint64_t P = 0xFFFFFFFF00000001ull;
-enum : uint16_t { LOAD_WIRE = 0, LOAD_CONST, LOAD_PI, LOAD_IMM, ADD, SUB, MUL, EMIT, MULK, ACC, ACCR };
-constexpr int MAX_REGS = 64;
-const u128 ACC_LIMIT = (u128)1 << 63;  // each half of an accumulator stays below this (gl::fold96's precondition)
+constexpr uint64_t P = glh::P;
+const u128 ACC_LIMIT = AccBound::LIMIT;  // each half of an accumulator stays below this (gl::fold96's precondition)
 
 // Field constants referenced by LOAD_IMM / ACC, shared by all gates of a circuit (deduplicated)
 struct ImmediatePool {
@@ -64,12 +66,12 @@ struct GateAsm {
     std::vector<GlGateInstr> instrs;
     ImmediatePool *pool;
     std::vector<int> free_list;
-    u128 acc_bound[4] = {0, 0, 0, 0};
+    AccBound acc_bound[MAX_ACCS];
 
     explicit GateAsm(ImmediatePool *p = nullptr) : pool(p) { release(); }
     void release() {
         free_list.clear();
-        for (int r = MAX_REGS - 1; r >= 0; r--) free_list.push_back(r);
+        for (int r = (int)MAX_REGS - 1; r >= 0; r--) free_list.push_back(r);
     }
     int reg() {
         if (free_list.empty()) throw std::runtime_error("gate program needs more than 64 live registers");
@@ -109,17 +111,16 @@ struct GateAsm {
     void emit(int a) { instrs.push_back(GlGateInstr{EMIT, 0, field(a), 0}); }
 
     // may r * weight still be added to accumulator q without either half being able to reach 2^63?
-    bool acc_fits(u128 weight, int q = 0) const { return weight < ((u128)1 << 32) && acc_bound[q] + weight * 0xFFFFFFFFull < ACC_LIMIT; }
+    bool acc_fits(u128 weight, int q = 0) const { return acc_bound[q].fits(weight); }
     // acc[q] += r[a] * weight, without a modular step (ACC): weight < 2^32, bound checked here
     void acc(int a, u128 weight = 1, int q = 0) {
         ImmediatePool &pl = need_pool();
-        if (!acc_fits(weight, q)) throw std::runtime_error("accumulator could overflow: reduce (accr) earlier");
-        acc_bound[q] += weight * 0xFFFFFFFFull;
+        if (!acc_bound[q].add(weight)) throw std::runtime_error("accumulator could overflow: reduce (accr) earlier");
         instrs.push_back(GlGateInstr{ACC, field(q), field(a), field((long)pl.index(weight))});
     }
     // register <- acc[q] mod p; acc[q] <- 0 (ACCR)
     int accr(int q = 0, int dst = -1) {
-        acc_bound[q] = 0;
+        acc_bound[q].reset();
         return op(ACCR, q, 0, dst);
     }
     // sum_i r[reg_i] * weight_i through accumulator q; reduces in between only if the static bound demands it
@@ -760,20 +761,13 @@ Program poseidon_mds_gate(ImmediatePool &pool) {
     return g.instrs;
 }
 
-uint64_t mulmod(uint64_t a, uint64_t b) { return (uint64_t)((u128)a * b % P); }
-uint64_t root_of_unity(unsigned bits) {  // F::primitive_root_of_unity (field/src/types.rs:268-272)
-    uint64_t r = 1753635133440165772ull;
-    for (unsigned i = bits; i < 32; i++) r = mulmod(r, r);
-    return r;
-}
-
 // HighDegreeInterpolationGate (plonky2/src/gates/high_degree_interpolation.rs:119-147) / LowDegreeInterpolationGate
 // (low_degree_interpolation.rs:356-404); wire layout gates/interpolation.rs:19-76
 Program interpolation_gate(unsigned subgroup_bits, ImmediatePool &pool, bool low_degree) {
     GateAsm g(&pool);
     const unsigned d = 2, np = 1u << subgroup_bits;
     const unsigned start_values = 1, eval_point = 1 + np * d, eval_value = eval_point + d, start_coeffs = eval_value + d, end_coeffs = start_coeffs + np * d;
-    const uint64_t w = root_of_unity(subgroup_bits);
+    const uint64_t w = glh::root_of_unity(subgroup_bits);
     const int shift = g.wire(0);
     // Horner with a base-field point in register x: acc = acc * x + c, component-wise; returns a fresh pair
     auto eval_base = [&](const std::vector<Ext> &cs, int x) {
@@ -810,7 +804,7 @@ Program interpolation_gate(unsigned subgroup_bits, ImmediatePool &pool, bool low
     uint64_t wi = 1;
     for (unsigned i = 0; i < np; i++) {
         const int x = g.imm(wi);
-        wi = mulmod(wi, w);
+        wi = glh::mul(wi, w);
         if (!low_degree) g.mul(x, shift, x);  // coset(shift) = g^i * shift
         const Ext computed = eval_base(coeffs, x);
         g.free1(x);
@@ -935,7 +929,6 @@ GlError emit_error(const std::string &msg) {
 // the two against each other word for word).
 namespace keccak_table {
 
-enum : uint16_t { LOAD_NEXT = 11, EMIT_TRANSITION = 12, EMIT_FIRST_ROW = 13 };
 constexpr int NUM_ROUNDS = 24;
 const uint64_t RC[NUM_ROUNDS] = {
     0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull, 0x000000000000808Bull, 0x0000000080000001ull,
@@ -1140,7 +1133,6 @@ Program program(ImmediatePool &pool) {
 // other word for word).
 namespace memory_table {
 
-enum : uint16_t { EMIT_LAST_ROW = 14 };
 // columns.rs
 enum {
     FILTER = 0,
@@ -1269,7 +1261,7 @@ GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePo
         ImmediatePool pool;
         const Program prog = build(pool);
         uint32_t emits = 0;
-        for (const GlGateInstr &in : prog) emits += in.op == EMIT || in.op >= keccak_table::EMIT_TRANSITION;
+        for (const GlGateInstr &in : prog) emits += is_emit(in.op);
         out->num_instrs = (uint32_t)prog.size();
         out->num_immediates = (uint32_t)pool.values.size();
         out->num_gate_constraints = emits;

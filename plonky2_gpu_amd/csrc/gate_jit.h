@@ -8,17 +8,6 @@
 
 namespace plonky2_hip {
 
-// What every run-time compiled kernel of the library shares (the gates here, a STARK's quotient in stark_jit.hip): where code
-// objects are kept ($PLONKY2_HIP_KERNEL_CACHE, else `kernel_cache` next to the library; "" = no cache), the file name
-// <dir>/<prefix><FNV-1a of hiprtc version + target + source> without its extension, the list $PLONKY2_HIP_KERNEL_CACHE_LIST
-// receives, the cached code object if there is one, and hiprtc itself (which writes <path>.hsaco and <path>.hip). None of them
-// touches a device.
-std::string jit_cache_dir();
-std::string jit_cache_path(const std::string &dir, const std::string &source, const char *prefix);
-void jit_cache_list(const std::vector<std::string> &cache_paths);
-bool jit_cache_read(const std::string &cache_path, std::vector<char> *code);
-bool jit_compile(const std::string &source, const char *program_name, const std::string &cache_path, std::vector<char> *code, std::string *error);
-
 struct GateKernel;  // opaque: hipModule + function + device table of alpha powers
 
 // instrs: 4 x u16 per instruction (op, dst, a, b); gates: 6 x u32 per gate (row, selector_index, group_start,

@@ -17,11 +17,7 @@
 // small device table read with wave-uniform (scalar) loads.
 #include "gate_jit.h"
 
-#include <hip/hiprtc.h>
-
-#include <dlfcn.h>
 #include <signal.h>
-#include <sys/stat.h>
 #include <sys/wait.h>
 #include <time.h>
 #include <unistd.h>
@@ -38,35 +34,18 @@
 #include <vector>
 
 #include "gl_field.h"
+#include "jit.h"
 #include "knobs.h"
+#include "program_isa.h"
 
 namespace plonky2_hip {
 
 namespace {
-const char *const GL_FIELD_SRC =
-#include "build/gl_field_src.inc"
-    ;
 const char *const GL_JIT_FIELD_SRC =
 #include "build/gate_jit_field_src.inc"
     ;
-
-enum : uint16_t { GP_LOAD_WIRE, GP_LOAD_CONST, GP_LOAD_PI, GP_LOAD_IMM, GP_ADD, GP_SUB, GP_MUL, GP_EMIT, GP_MULK, GP_ACC, GP_ACCR };
-constexpr uint32_t MAX_REGS = 64, MAX_CH = 4;
-const char *const JIT_ARCH = "gfx950";
-
-// Where compiled code objects are kept: $PLONKY2_HIP_KERNEL_CACHE (empty = no cache), else the directory
-// `kernel_cache` next to this shared library if it exists — the place __graft_entry__.build() precompiles the
-// compiled-in ed25519 gate kernel into, so that it ships with the library like any ahead-of-time kernel.
-std::string kernel_cache_dir() {
-    if (const char *dir = getenv("PLONKY2_HIP_KERNEL_CACHE")) return dir;
-    Dl_info info;
-    if (!dladdr(reinterpret_cast<const void *>(&kernel_cache_dir), &info) || !info.dli_fname) return "";
-    std::string lib(info.dli_fname);
-    size_t slash = lib.rfind('/');
-    std::string dir = (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/kernel_cache";
-    struct stat st;
-    return (stat(dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) ? dir : "";
-}
+using isa::MAX_REGS;
+constexpr uint32_t MAX_CH = 4;
 }  // namespace
 
 // A circuit's gates are compiled as several UNITS — each a hiprtc program of its own with some of the gates and a kernel
@@ -130,16 +109,18 @@ bool gate_programs_validate(const uint16_t *instrs, uint32_t num_instrs, const u
         // program order (a program that leans on registers starting at zero would build under one generator setting and not the other).
         bool written[MAX_REGS] = {};
         for (uint32_t pc = ps; pc < ps + pl; pc++) {
-            const uint16_t op = instrs[4 * pc], dst = instrs[4 * pc + 1], a = instrs[4 * pc + 2], b = instrs[4 * pc + 3];
-            const bool reads_a = op == GP_ADD || op == GP_SUB || op == GP_MUL || op == GP_EMIT || op == GP_MULK || op == GP_ACC;
-            const bool reads_b = op == GP_ADD || op == GP_SUB || op == GP_MUL;
+            const auto [op, dst, a, b] = isa::instr_at(instrs, pc);
+            if (op > isa::ACCR) {  // 11..14 are opcodes of STARK programs only
+                *error = "unknown opcode";
+                return false;
+            }
+            const bool reads_a = isa::reads_a(op), reads_b = isa::reads_b(op), writes = isa::writes_reg(op);
             // Indices are taken as written: the interpreter and the generators mask them (& 63, & 3) for memory safety only, and a program
             // that leaned on the masking would mean different things to them (the per-gate generator shifts a MULK by up to 95).
-            const bool writes = op != GP_EMIT && op != GP_ACC && op <= GP_ACCR;
             const char *range = (reads_a && a >= MAX_REGS) || (reads_b && b >= MAX_REGS) || (writes && dst >= MAX_REGS) ? "register index >= 64"
-                                : (op == GP_ACC && dst >= 4) || (op == GP_ACCR && a >= 4)                              ? "accumulator index >= 4"
-                                : (op == GP_MULK && b >= 64)                                                           ? "MULK shift >= 64"
-                                : (op == GP_LOAD_PI && a >= 4)                                                         ? "LOAD_PI index >= 4"
+                                : (isa::acc_in_dst(op) && dst >= isa::MAX_ACCS) || (isa::acc_in_a(op) && a >= isa::MAX_ACCS) ? "accumulator index >= 4"
+                                : (op == isa::MULK && b >= 64)                                                           ? "MULK shift >= 64"
+                                : (op == isa::LOAD_PI && a >= 4)                                                         ? "LOAD_PI index >= 4"
                                                                                                                        : nullptr;
             if (range) {
                 *error = "gate " + std::to_string(g) + ": " + range + " (instruction " + std::to_string(pc - ps) + ")";
@@ -149,22 +130,18 @@ bool gate_programs_validate(const uint16_t *instrs, uint32_t num_instrs, const u
                 *error = "gate " + std::to_string(g) + ": register read before any write (instruction " + std::to_string(pc - ps) + ")";
                 return false;
             }
-            if (op != GP_EMIT && op != GP_ACC && op <= GP_ACCR) written[dst & (MAX_REGS - 1)] = true;  // ACC's dst names an accumulator
-            if (op == GP_LOAD_WIRE && (uint32_t)a + 1 > wn) wn = (uint32_t)a + 1;
-            if (op == GP_LOAD_CONST && num_selectors + a + 1 > cn) cn = num_selectors + a + 1;
-            if (op == GP_LOAD_IMM && a >= num_imms) {
+            if (writes) written[dst & (MAX_REGS - 1)] = true;
+            if (op == isa::LOAD_WIRE && (uint32_t)a + 1 > wn) wn = (uint32_t)a + 1;
+            if (op == isa::LOAD_CONST && num_selectors + a + 1 > cn) cn = num_selectors + a + 1;
+            if (op == isa::LOAD_IMM && a >= num_imms) {
                 *error = "LOAD_IMM index out of range";
                 return false;
             }
-            if (op == GP_ACC && b >= num_imms) {
+            if (op == isa::ACC && b >= num_imms) {
                 *error = "ACC immediate index out of range";
                 return false;
             }
-            if (op == GP_EMIT) emitted++;
-            if (op > GP_ACCR) {
-                *error = "unknown opcode";
-                return false;
-            }
+            if (op == isa::EMIT) emitted++;
         }
         if (emitted > ngc) {
             *error = "gate " + std::to_string(g) + " emits " + std::to_string(emitted) + " constraints but num_gate_constraints is " +
@@ -213,41 +190,39 @@ static std::vector<Peep> peephole(const uint16_t *instrs, uint32_t ps, uint32_t 
     std::vector<std::vector<uint32_t>> uses(pl);
     int last[MAX_REGS];
     for (uint32_t r = 0; r < MAX_REGS; r++) last[r] = -1;
-    auto op_of = [&](uint32_t i) { return instrs[4 * (ps + i)]; };
-    auto fld = [&](uint32_t i, int f) { return instrs[4 * (ps + i) + f]; };
+    auto op_of = [&](uint32_t i) { return isa::instr_at(instrs, ps + i).op; };
+    auto fld = [&](uint32_t i, int f) { return instrs[4 * (ps + i) + f]; };  // 1: dst, 2: a, 3: b
     for (uint32_t i = 0; i < pl; i++) {
         const uint16_t op = op_of(i);
-        const bool reads_a = op == GP_ADD || op == GP_SUB || op == GP_MUL || op == GP_EMIT || op == GP_MULK || op == GP_ACC;
-        const bool reads_b = op == GP_ADD || op == GP_SUB || op == GP_MUL;
-        if (reads_a && (def_a[i] = last[fld(i, 2) & (MAX_REGS - 1)]) >= 0) uses[def_a[i]].push_back(i);
-        if (reads_b && (def_b[i] = last[fld(i, 3) & (MAX_REGS - 1)]) >= 0) uses[def_b[i]].push_back(i);
-        if (op != GP_EMIT && op != GP_ACC) last[fld(i, 1) & (MAX_REGS - 1)] = (int)i;  // ACC's dst names an accumulator
+        if (isa::reads_a(op) && (def_a[i] = last[fld(i, 2) & (MAX_REGS - 1)]) >= 0) uses[def_a[i]].push_back(i);
+        if (isa::reads_b(op) && (def_b[i] = last[fld(i, 3) & (MAX_REGS - 1)]) >= 0) uses[def_b[i]].push_back(i);
+        if (isa::writes_reg(op)) last[fld(i, 1) & (MAX_REGS - 1)] = (int)i;  // all but EMIT and ACC: validated, opcodes 0..10 only
     }
     auto small_imm = [&](int d, uint64_t *v) {
-        if (d < 0 || op_of(d) != GP_LOAD_IMM || fld(d, 2) >= num_imms) return false;
+        if (d < 0 || op_of(d) != isa::LOAD_IMM || fld(d, 2) >= num_imms) return false;
         *v = imms[fld(d, 2)] % glh::P;
         return *v <= 0xFFFFFFFFull;
     };
     for (uint32_t i = 0; i < pl; i++) {
         const uint16_t op = op_of(i);
         uint64_t v = 0;
-        if (op == GP_ADD || op == GP_SUB) {
+        if (op == isa::ADD || op == isa::SUB) {
             const bool b_small = small_imm(def_b[i], &v);
-            const bool a_small = !b_small && op == GP_ADD && small_imm(def_a[i], &v);
+            const bool a_small = !b_small && op == isa::ADD && small_imm(def_a[i], &v);
             if (!b_small && !a_small) continue;
             const int other = b_small ? def_a[i] : def_b[i];
             if (other < 0) continue;  // read before any write: left to the generator's own check
-            out[i].kind = v == 0 ? Peep::COPY : op == GP_ADD ? Peep::ADD_SMALL : Peep::SUB_SMALL;
+            out[i].kind = v == 0 ? Peep::COPY : op == isa::ADD ? Peep::ADD_SMALL : Peep::SUB_SMALL;
             out[i].src = fld(i, b_small ? 2 : 3) & (MAX_REGS - 1);
             out[i].src_def = other;
             out[i].k = v;
         }
     }
     for (uint32_t m2 = 0; m2 < pl; m2++) {
-        if (op_of(m2) != GP_MUL || def_a[m2] < 0 || def_b[m2] < 0) continue;
+        if (op_of(m2) != isa::MUL || def_a[m2] < 0 || def_b[m2] < 0) continue;
         for (int swap = 0; swap < 2; swap++) {
             const int m1 = swap ? def_b[m2] : def_a[m2], ad = swap ? def_a[m2] : def_b[m2];
-            if (m1 == ad || op_of(m1) != GP_MUL || op_of(ad) != GP_ADD) continue;
+            if (m1 == ad || op_of(m1) != isa::MUL || op_of(ad) != isa::ADD) continue;
             // the ADD is t + 2 with t the very value of m1
             uint64_t v = 0;
             const bool t_is_a = def_a[ad] == m1 && small_imm(def_b[ad], &v) && v == 2;
@@ -255,7 +230,7 @@ static std::vector<Peep> peephole(const uint16_t *instrs, uint32_t ps, uint32_t 
             if (!t_is_a && !t_is_b) continue;
             if (uses[m1].size() != 2 || uses[ad].size() != 1 || uses[m2].size() != 1) continue;  // (m1: the ADD and m2; each once)
             const uint32_t e = uses[m2][0];
-            if (op_of(e) != GP_EMIT || def_a[m1] < 0 || def_b[m1] < 0) continue;
+            if (op_of(e) != isa::EMIT || def_a[m1] < 0 || def_b[m1] < 0) continue;
             if (out[m1].kind != Peep::PLAIN || out[m2].kind != Peep::PLAIN) continue;  // m1 already rewritten as another limb's square
             out[m1].kind = Peep::MUL_ADD1;
             out[ad].kind = Peep::SKIP;
@@ -269,24 +244,24 @@ static std::vector<Peep> peephole(const uint16_t *instrs, uint32_t ps, uint32_t 
     // 3. what is left of MUL / ADD / SUB with a LOAD_IMM operand takes the constant as a scalar operand (gl::mul_k, gl::add_k; x - K is
     //    x + (p - K)), and a LOAD_IMM that nothing reads any more is not generated.
     auto any_imm = [&](int d, uint64_t *v) {
-        if (d < 0 || op_of(d) != GP_LOAD_IMM || fld(d, 2) >= num_imms) return false;
+        if (d < 0 || op_of(d) != isa::LOAD_IMM || fld(d, 2) >= num_imms) return false;
         *v = imms[fld(d, 2)] % glh::P;
         return true;
     };
     for (uint32_t i = 0; i < pl; i++) {
         const uint16_t op = op_of(i);
-        if ((op != GP_MUL && op != GP_ADD && op != GP_SUB) || out[i].kind != Peep::PLAIN || def_a[i] < 0 || def_b[i] < 0) continue;
+        if ((op != isa::MUL && op != isa::ADD && op != isa::SUB) || out[i].kind != Peep::PLAIN || def_a[i] < 0 || def_b[i] < 0) continue;
         uint64_t v = 0;
         const bool b_imm = any_imm(def_b[i], &v);
-        const bool a_imm = !b_imm && op != GP_SUB && any_imm(def_a[i], &v);
+        const bool a_imm = !b_imm && op != isa::SUB && any_imm(def_a[i], &v);
         if (!b_imm && !a_imm) continue;
-        out[i].kind = op == GP_MUL ? Peep::MUL_K : Peep::ADD_K;
+        out[i].kind = op == isa::MUL ? Peep::MUL_K : Peep::ADD_K;
         out[i].src = fld(i, b_imm ? 2 : 3) & (MAX_REGS - 1);
         out[i].src_def = b_imm ? def_a[i] : def_b[i];
-        out[i].k = op == GP_SUB ? (glh::P - v) % glh::P : v;
+        out[i].k = op == isa::SUB ? (glh::P - v) % glh::P : v;
     }
     for (uint32_t d = 0; d < pl; d++) {
-        if (op_of(d) != GP_LOAD_IMM) continue;
+        if (op_of(d) != isa::LOAD_IMM) continue;
         bool read = false;
         for (uint32_t u : uses[d]) {
             const Peep::Kind kd = out[u].kind;
@@ -391,28 +366,29 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
     const std::vector<Peep> peep = peephole(instrs, ps, pl, imms, num_imms);
     uint32_t reg[MAX_REGS];
     for (uint32_t r = 0; r < MAX_REGS; r++) reg[r] = ~0u;
-    std::vector<std::pair<uint32_t, uint64_t>> acc[4];
-    bool acc_used[4] = {};
-    unsigned __int128 acc_bound[4] = {0, 0, 0, 0};
+    std::vector<std::pair<uint32_t, uint64_t>> acc[isa::MAX_ACCS];
+    bool acc_used[isa::MAX_ACCS] = {};
+    isa::AccBound acc_bound[isa::MAX_ACCS];
     uint32_t k = 0;
     for (uint32_t pc = ps; pc < ps + pl; pc++) {
-        const uint16_t op = instrs[4 * pc], dst = instrs[4 * pc + 1] & (MAX_REGS - 1), a = instrs[4 * pc + 2], b = instrs[4 * pc + 3];
+        const isa::Instr in = isa::instr_at(instrs, pc);
+        const uint16_t op = in.op, dst = in.dst & (MAX_REGS - 1), a = in.a, b = in.b;
         const uint32_t ra = a & (MAX_REGS - 1), rb = b & (MAX_REGS - 1);
         const Peep &pp = peep[pc - ps];
         switch (op) {
-            case GP_LOAD_WIRE: reg[dst] = g.make(FNode::WIRE, a); break;
-            case GP_LOAD_CONST: reg[dst] = g.make(FNode::CONST, a); break;
-            case GP_LOAD_PI: reg[dst] = g.make(FNode::PI, a & 3); break;
-            case GP_LOAD_IMM:
+            case isa::LOAD_WIRE: reg[dst] = g.make(FNode::WIRE, a); break;
+            case isa::LOAD_CONST: reg[dst] = g.make(FNode::CONST, a); break;
+            case isa::LOAD_PI: reg[dst] = g.make(FNode::PI, a & 3); break;
+            case isa::LOAD_IMM:
                 if (a >= num_imms) {
                     *error = "LOAD_IMM index out of range";
                     return false;
                 }
                 reg[dst] = g.make(FNode::IMM, ~0u, ~0u, imms[a] % glh::P);
                 break;
-            case GP_ADD:
-            case GP_SUB:
-            case GP_MUL:
+            case isa::ADD:
+            case isa::SUB:
+            case isa::MUL:
                 // (a rewritten range check's c = t * u reads u, the t + 2 that is not generated: when the program wrote u to a register
                 // nothing had written before, that register holds no node — the square takes t alone)
                 if (pp.kind == Peep::SQUARE ? reg[pp.src] == ~0u : (reg[ra] == ~0u || reg[rb] == ~0u)) {
@@ -420,7 +396,7 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
                     return false;
                 }
                 switch (pp.kind) {
-                    case Peep::PLAIN: reg[dst] = g.make(op == GP_ADD ? FNode::ADD : op == GP_SUB ? FNode::SUB : FNode::MUL, reg[ra], reg[rb]); break;
+                    case Peep::PLAIN: reg[dst] = g.make(op == isa::ADD ? FNode::ADD : op == isa::SUB ? FNode::SUB : FNode::MUL, reg[ra], reg[rb]); break;
                     case Peep::ADD_SMALL: reg[dst] = g.make(FNode::ADD_SMALL, reg[pp.src], ~0u, pp.k); break;
                     case Peep::SUB_SMALL: reg[dst] = g.make(FNode::SUB_SMALL, reg[pp.src], ~0u, pp.k); break;
                     case Peep::COPY: reg[dst] = reg[pp.src]; break;
@@ -431,7 +407,7 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
                     case Peep::SKIP: break;  // t + 2 of a range check: read by nothing that is still generated
                 }
                 break;
-            case GP_EMIT:
+            case isa::EMIT:
                 if (reg[ra] == ~0u) {
                     *error = "register read before any write";
                     return false;
@@ -440,14 +416,13 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
                 if (pp.bias) bias->push_back({k, pp.bias});
                 k++;
                 break;
-            case GP_ACC: {
-                const uint32_t q = instrs[4 * pc + 1] & 3;
+            case isa::ACC: {
+                const uint32_t q = in.dst & (isa::MAX_ACCS - 1);
                 if (reg[ra] == ~0u || b >= num_imms || imms[b] > 0xFFFFFFFFull) {
                     *error = "ACC: register read before any write, or the immediate is missing / not below 2^32";
                     return false;
                 }
-                acc_bound[q] += (unsigned __int128)imms[b] * 0xFFFFFFFFull;
-                if (acc_bound[q] >> 63) {
+                if (!acc_bound[q].add(imms[b])) {
                     *error = "ACC: the accumulator could reach 2^63 before its ACCR";
                     return false;
                 }
@@ -455,8 +430,8 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
                 acc_used[q] = true;
                 break;
             }
-            case GP_ACCR: {
-                const uint32_t q = a & 3;
+            case isa::ACCR: {
+                const uint32_t q = a & (isa::MAX_ACCS - 1);
                 if (!acc_used[q]) {
                     *error = "ACCR of an accumulator nothing was added to";
                     return false;
@@ -467,10 +442,10 @@ static bool fuse_gate(FGraph &g, const uint16_t *instrs, uint32_t ps, uint32_t p
                 std::sort(n.terms.begin(), n.terms.end());
                 reg[dst] = g.intern(n);
                 acc[q].clear();
-                acc_bound[q] = 0;
+                acc_bound[q].reset();
                 break;
             }
-            case GP_MULK:
+            case isa::MULK:
                 if (reg[ra] == ~0u || b >= 96) {
                     *error = "MULK: register read before any write, or shift >= 96";
                     return false;
@@ -689,7 +664,7 @@ static std::string generate_fused_source(const uint16_t *instrs, uint32_t num_in
                                          const uint64_t *imms, uint32_t num_imms, uint32_t num_selectors, uint32_t ngc, uint32_t nch,
                                          std::vector<std::vector<std::pair<uint32_t, uint64_t>>> *bias, std::string *error) {
     std::ostringstream o;
-    o << "#define GL_JIT 1\n" << GL_FIELD_SRC << "\n" << GL_JIT_FIELD_SRC << "\n";
+    o << "#define GL_JIT 1\n" << jit_field_source() << "\n" << GL_JIT_FIELD_SRC << "\n";
     o << "#define NGU " << unit_gates.size() << "\n#define NCH " << nch << "\n#define NGC " << ngc << "\n";
     // g_apow[c][k] = {alpha_c^k, alpha_c^k * 2^32}: the two-column accumulators of gate_jit_field.h (gl::DotCol2)
     // ONE constant object per unit — LDE pointers and strides, public-inputs hash, alpha powers, biases — so that a launch uploads
@@ -747,7 +722,7 @@ static std::string generate_source(const uint16_t *instrs, uint32_t num_instrs, 
                                    std::vector<std::vector<std::pair<uint32_t, uint64_t>>> *bias, std::string *error) {
     if (fuse_enabled()) return generate_fused_source(instrs, num_instrs, gates, unit_gates, imms, num_imms, num_selectors, ngc, nch, bias, error);
     std::ostringstream o;
-    o << "#define GL_JIT 1\n" << GL_FIELD_SRC << "\n" << GL_JIT_FIELD_SRC << "\n";
+    o << "#define GL_JIT 1\n" << jit_field_source() << "\n" << GL_JIT_FIELD_SRC << "\n";
     o << "#define NGU " << unit_gates.size() << "\n";
     bias->assign(unit_gates.size(), {});
     o << "#define NCH " << nch << "\n#define NGC " << ngc << "\n";
@@ -788,25 +763,27 @@ static std::string generate_source(const uint16_t *instrs, uint32_t num_instrs, 
         // vector instructions and 2.5 % SLOWER: a v_mad_u64_u32 costs about two plain instructions here. LABNOTES.md 10.)
         o << "  gl::DotAcc ga[NCH];\n";
         bool used[MAX_REGS] = {};
-        bool acc_used[4] = {};
+        bool acc_used[isa::MAX_ACCS] = {};
         for (uint32_t pc = ps; pc < ps + pl; pc++) {
-            if (instrs[4 * pc] == GP_ACC)  // its dst field names an accumulator, not a register
-                acc_used[instrs[4 * pc + 1] & 3] = true;
-            else
-                used[instrs[4 * pc + 1] & (MAX_REGS - 1)] = true;
+            const isa::Instr in = isa::instr_at(instrs, pc);
+            if (isa::acc_in_dst(in.op))
+                acc_used[in.dst & (isa::MAX_ACCS - 1)] = true;
+            else  // an EMIT's dst as well: a register the program only names is declared, at zero
+                used[in.dst & (MAX_REGS - 1)] = true;
         }
-        for (int q = 0; q < 4; q++)
+        for (uint32_t q = 0; q < isa::MAX_ACCS; q++)
             if (acc_used[q]) o << "  uint64_t acc" << q << "l = 0, acc" << q << "h = 0;\n";
         // worst case of each accumulator half: sum of imm * (2^32 - 1) since its last ACCR; gl::fold96 needs < 2^63
-        unsigned __int128 acc_bound[4] = {0, 0, 0, 0};
+        isa::AccBound acc_bound[isa::MAX_ACCS];
         for (uint32_t r = 0; r < MAX_REGS; r++)
             if (used[r]) o << "  uint64_t r" << r << " = 0;\n";
         uint32_t k = 0;
         for (uint32_t pc = ps; pc < ps + pl; pc++) {
-            const uint16_t op = instrs[4 * pc], dst = instrs[4 * pc + 1] & (MAX_REGS - 1), a = instrs[4 * pc + 2], b = instrs[4 * pc + 3];
+            const isa::Instr in = isa::instr_at(instrs, pc);
+            const uint16_t op = in.op, dst = in.dst & (MAX_REGS - 1), a = in.a, b = in.b;
             const uint32_t ra = a & (MAX_REGS - 1), rb = b & (MAX_REGS - 1);
             const Peep &pp = peep[pc - ps];
-            if (pp.kind != Peep::PLAIN && (op == GP_ADD || op == GP_SUB || op == GP_MUL)) {
+            if (pp.kind != Peep::PLAIN && (op == isa::ADD || op == isa::SUB || op == isa::MUL)) {
                 if (!used[ra] || !used[rb]) {
                     *error = "register read before any write";
                     return "";
@@ -823,29 +800,29 @@ static std::string generate_source(const uint16_t *instrs, uint32_t num_instrs, 
                 }
                 continue;
             }
-            if (pp.kind == Peep::SKIP && op == GP_LOAD_IMM) continue;  // every reader takes the constant as an operand
+            if (pp.kind == Peep::SKIP && op == isa::LOAD_IMM) continue;  // every reader takes the constant as an operand
             switch (op) {
-                case GP_LOAD_WIRE: o << "  r" << dst << " = W[" << a << " * wes];\n"; break;
-                case GP_LOAD_CONST: o << "  r" << dst << " = C[" << (num_selectors + a) << " * ces];\n"; break;
-                case GP_LOAD_PI: o << "  r" << dst << " = g_pih[" << (a & 3) << "];\n"; break;
-                case GP_LOAD_IMM:
+                case isa::LOAD_WIRE: o << "  r" << dst << " = W[" << a << " * wes];\n"; break;
+                case isa::LOAD_CONST: o << "  r" << dst << " = C[" << (num_selectors + a) << " * ces];\n"; break;
+                case isa::LOAD_PI: o << "  r" << dst << " = g_pih[" << (a & 3) << "];\n"; break;
+                case isa::LOAD_IMM:
                     if (a >= num_imms) {
                         *error = "LOAD_IMM index out of range";
                         return "";
                     }
                     o << "  r" << dst << " = 0x" << std::hex << (imms[a] % glh::P) << std::dec << "ull;\n";
                     break;
-                case GP_ADD:
-                case GP_SUB:
-                case GP_MUL:
+                case isa::ADD:
+                case isa::SUB:
+                case isa::MUL:
                     if (!used[ra] || !used[rb]) {
                         *error = "register read before any write";
                         return "";
                     }
-                    o << "  r" << dst << " = gl::" << (op == GP_ADD ? "add" : op == GP_SUB ? "sub" : "mul") << "(r" << ra << ", r" << rb
+                    o << "  r" << dst << " = gl::" << (op == isa::ADD ? "add" : op == isa::SUB ? "sub" : "mul") << "(r" << ra << ", r" << rb
                       << ");\n";
                     break;
-                case GP_EMIT:
+                case isa::EMIT:
                     if (!used[ra]) {
                         *error = "register read before any write";
                         return "";
@@ -854,14 +831,13 @@ static std::string generate_source(const uint16_t *instrs, uint32_t num_instrs, 
                     if (pp.bias) (*bias)[gi].push_back({k, pp.bias});
                     k++;
                     break;
-                case GP_ACC: {  // acc[dst] += r[a] * imm[b]: two 32x32+64 multiply-adds, no modular step
-                    const uint32_t q = instrs[4 * pc + 1] & 3;
+                case isa::ACC: {  // acc[dst] += r[a] * imm[b]: two 32x32+64 multiply-adds, no modular step
+                    const uint32_t q = in.dst & (isa::MAX_ACCS - 1);
                     if (!used[ra] || b >= num_imms || imms[b] > 0xFFFFFFFFull) {
                         *error = "ACC: register read before any write, or the immediate is missing / not below 2^32";
                         return "";
                     }
-                    acc_bound[q] += (unsigned __int128)imms[b] * 0xFFFFFFFFull;
-                    if (acc_bound[q] >> 63) {
+                    if (!acc_bound[q].add(imms[b])) {
                         *error = "ACC: the accumulator could reach 2^63 before its ACCR";
                         return "";
                     }
@@ -870,17 +846,17 @@ static std::string generate_source(const uint16_t *instrs, uint32_t num_instrs, 
                     o << "  gj_acc(acc" << q << "l, acc" << q << "h, r" << ra << ", " << imms[b] << "u);\n";
                     break;
                 }
-                case GP_ACCR: {  // r[dst] = acc[a] mod p; acc[a] = 0
-                    const uint32_t q = a & 3;
+                case isa::ACCR: {  // r[dst] = acc[a] mod p; acc[a] = 0
+                    const uint32_t q = a & (isa::MAX_ACCS - 1);
                     if (!acc_used[q]) {
                         *error = "ACCR of an accumulator nothing was added to";
                         return "";
                     }
                     o << "  r" << dst << " = gl::fold96(acc" << q << "l, acc" << q << "h); acc" << q << "l = 0; acc" << q << "h = 0;\n";
-                    acc_bound[q] = 0;
+                    acc_bound[q].reset();
                     break;
                 }
-                case GP_MULK:
+                case isa::MULK:
                     if (!used[ra] || b >= 96) {
                         *error = "MULK: register read before any write, or shift >= 96";
                         return "";
@@ -916,86 +892,6 @@ static uint32_t jit_unit_limit() {
     }
     const unsigned hw = std::thread::hardware_concurrency();
     return hw == 0 ? 4 : hw > 8 ? 8 : hw;
-}
-
-// Cache file name of a compiled source (kernel_cache_dir()): keyed by a hash of the generated source and of what turns the same
-// source into a different code object — the hiprtc version and the target. `prefix`: "gate_" for a circuit's units, "stark_" for a
-// STARK's quotient kernel (stark_jit.hip).
-std::string jit_cache_dir() { return kernel_cache_dir(); }
-
-std::string jit_cache_path(const std::string &dir, const std::string &source, const char *prefix) {
-    if (dir.empty()) return "";
-    int rtc_major = 0, rtc_minor = 0;
-    (void)hiprtcVersion(&rtc_major, &rtc_minor);
-    const std::string salt = "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + " " + JIT_ARCH + "\n";
-    uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a
-    for (unsigned char ch : salt) h = (h ^ ch) * 0x100000001b3ull;
-    for (unsigned char ch : source) h = (h ^ ch) * 0x100000001b3ull;
-    char name[64];
-    snprintf(name, sizeof name, "/%s%016llx", prefix, (unsigned long long)h);
-    return dir + name;
-}
-
-// $PLONKY2_HIP_KERNEL_CACHE_LIST=<file>: the cache entries this build uses, one path per line (appended) — how build() tells the
-// current generator's units from whatever else the cache directory holds without compiling anything twice (__graft_entry__.py)
-void jit_cache_list(const std::vector<std::string> &cache_paths) {
-    if (const char *lf = getenv("PLONKY2_HIP_KERNEL_CACHE_LIST"))
-        if (FILE *f = fopen(lf, "a")) {
-            for (const std::string &cp : cache_paths)
-                if (!cp.empty()) fprintf(f, "%s\n", cp.c_str());
-            fclose(f);
-        }
-}
-
-bool jit_cache_read(const std::string &cache_path, std::vector<char> *code) {
-    if (cache_path.empty()) return false;
-    std::ifstream f(cache_path + ".hsaco", std::ios::binary);
-    if (f) code->assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-    return !code->empty();
-}
-
-// hiprtc on one source; the code object (and the source, for inspection) goes to the cache. May run on a thread of its own.
-bool jit_compile(const std::string &source, const char *program_name, const std::string &cache_path, std::vector<char> *code, std::string *error) {
-    hiprtcProgram prog;
-    hiprtcResult r = hiprtcCreateProgram(&prog, source.c_str(), program_name, 0, nullptr, nullptr);
-    if (r != HIPRTC_SUCCESS) {
-        *error = std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r);
-        return false;
-    }
-    const std::string arch = std::string("--offload-arch=") + JIT_ARCH;
-    const char *opts[] = {arch.c_str(), "-O3", "-std=c++17"};
-    r = hiprtcCompileProgram(prog, 3, opts);
-    if (r != HIPRTC_SUCCESS) {
-        size_t ls = 0;
-        hiprtcGetProgramLogSize(prog, &ls);
-        std::string log(ls, '\0');
-        if (ls) hiprtcGetProgramLog(prog, &log[0]);
-        *error = std::string("hiprtcCompileProgram: ") + hiprtcGetErrorString(r) + "\n" + log.substr(0, 4000);
-        hiprtcDestroyProgram(&prog);
-        return false;
-    }
-    size_t cs = 0;
-    hiprtcGetCodeSize(prog, &cs);
-    code->resize(cs);
-    hiprtcGetCode(prog, code->data());
-    hiprtcDestroyProgram(&prog);
-    if (!cache_path.empty()) {
-        // Several processes (one per GPU) may build the same circuit at once: each writes a file of its own and
-        // renames it into place, so a reader sees either nothing or a whole code object.
-        const std::string pid = std::to_string((long long)getpid()) + "." + std::to_string((unsigned long long)(uintptr_t)code);
-        const std::string tmp = cache_path + ".tmp." + pid, tmp_src = cache_path + ".hip." + pid;
-        std::ofstream(tmp_src) << source;
-        (void)rename(tmp_src.c_str(), (cache_path + ".hip").c_str());
-        bool written = false;
-        {
-            std::ofstream f(tmp, std::ios::binary);
-            f.write(code->data(), (std::streamsize)code->size());
-            f.flush();
-            written = f.good();
-        }
-        if (!written || rename(tmp.c_str(), (cache_path + ".hsaco").c_str()) != 0) (void)remove(tmp.c_str());
-    }
-    return true;
 }
 
 static std::string unit_cache_path(const std::string &dir, const std::string &source) { return jit_cache_path(dir, source, "gate_"); }
@@ -1148,7 +1044,7 @@ GateKernel *gate_kernel_build(const uint16_t *instrs, uint32_t num_instrs, const
         }
         k->units.erase(std::remove_if(k->units.begin(), k->units.end(), [](const GateUnit &u) { return u.gates.empty(); }), k->units.end());
     }
-    const std::string dir = kernel_cache_dir();
+    const std::string dir = jit_cache_dir();
     std::vector<std::string> cache_paths;
     for (GateUnit &u : k->units) {
         std::sort(u.gates.begin(), u.gates.end());

@@ -10,6 +10,10 @@ namespace plonky2_hip {
 
 uint32_t num_partial_products(uint32_t num_routed, uint32_t degree);
 
+// host: the 2^qdb values Z_H takes on the coset shift * <w_{n 2^qdb}> and their inverses, Z_H(x_i) = shift^n * w^(i mod 2^qdb) - 1
+// with w = w_{2^qdb} (field/src/zero_poly_coset.rs:20-41); the STARK quotient (stark.hip) stands on the same coset
+void zh_on_coset(uint64_t shift_pow_n, uint32_t qdb, uint64_t *zh, uint64_t *zh_inv);
+
 // out: [num_challenges * (1 + num_prods)][n] column-major in the reference's zs_partial_products order
 // (all Z first, then the partial products challenge-major; plonky2/src/plonk/prover.rs:106-117).
 hipError_t permutation_partial_products(const NttTables &tb, const uint64_t *wires, uint64_t wires_stride, const uint64_t *sigmas,

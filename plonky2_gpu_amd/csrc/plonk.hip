@@ -16,6 +16,7 @@
 
 #include "gl_field.h"
 #include "plonk_device.h"
+#include "program_isa.h"
 
 namespace plonky2_hip {
 
@@ -117,8 +118,7 @@ __global__ __launch_bounds__(256) void perm_finalize_kernel(uint64_t *out, const
 // over Gate::eval_filtered (gates/gate.rs:86-109) and compute_filter (gates/gate.rs:261-268). Every gate of
 // the circuit is a small register program (see plonky2_gpu_amd/gate_program.py for the instruction set);
 // all lanes of a wavefront execute the same instruction stream, so the interpreter does not diverge.
-constexpr int GP_MAX_REGS = 64, GP_MAX_CONSTRAINTS = 256;
-enum : uint16_t { GP_LOAD_WIRE, GP_LOAD_CONST, GP_LOAD_PI, GP_LOAD_IMM, GP_ADD, GP_SUB, GP_MUL, GP_EMIT, GP_MULK, GP_ACC, GP_ACCR };
+constexpr int GP_MAX_CONSTRAINTS = 256;
 
 struct GateProgramDev {
     const uint16_t *instrs;  // 4 x u16 per instruction: op, dst, a, b
@@ -130,7 +130,7 @@ struct GateProgramDev {
 
 __device__ void eval_gate_program(const GateProgramDev &gp, const uint64_t *local_constants, uint64_t c_es,
                                   const uint64_t *local_wires, uint64_t w_es, uint64_t *acc) {
-    uint64_t regs[GP_MAX_REGS];
+    uint64_t regs[isa::MAX_REGS];
     for (uint32_t k = 0; k < gp.num_gate_constraints; k++) acc[k] = 0;
     for (uint32_t g = 0; g < gp.num_gates; g++) {
         const uint32_t *d = gp.gates + 6 * g;
@@ -141,31 +141,31 @@ __device__ void eval_gate_program(const GateProgramDev &gp, const uint64_t *loca
             if (i != row) filt = gl::mul(filt, gl::sub(i, s));
         if (gp.num_selectors > 1) filt = gl::mul(filt, gl::sub(0xFFFFFFFFull, s));  // UNUSED_SELECTOR, selectors.rs:11
         uint32_t k = 0;
-        uint64_t acc_lo[4] = {0, 0, 0, 0}, acc_hi[4] = {0, 0, 0, 0};  // GP_ACC: plain (wrapping-free by contract) column sums
+        uint64_t acc_lo[4] = {0, 0, 0, 0}, acc_hi[4] = {0, 0, 0, 0};  // ACC: plain (wrapping-free by contract) column sums
         for (uint32_t pc = ps; pc < ps + pl; pc++) {
             const uint16_t *in = gp.instrs + 4 * pc;
-            const uint16_t op = in[0], dst = in[1] & (GP_MAX_REGS - 1), a = in[2], b = in[3];
+            const uint16_t op = in[0], dst = in[1] & (isa::MAX_REGS - 1), a = in[2], b = in[3];
             switch (op) {
-                case GP_LOAD_WIRE: regs[dst] = local_wires[a * w_es]; break;
-                case GP_LOAD_CONST: regs[dst] = local_constants[(gp.num_selectors + a) * c_es]; break;
-                case GP_LOAD_PI: regs[dst] = gp.pih[a & 3]; break;
-                case GP_LOAD_IMM: regs[dst] = gp.imms[a]; break;
-                case GP_ADD: regs[dst] = gl::add(regs[a & (GP_MAX_REGS - 1)], regs[b & (GP_MAX_REGS - 1)]); break;
-                case GP_SUB: regs[dst] = gl::sub(regs[a & (GP_MAX_REGS - 1)], regs[b & (GP_MAX_REGS - 1)]); break;
-                case GP_MUL: regs[dst] = gl::mul(regs[a & (GP_MAX_REGS - 1)], regs[b & (GP_MAX_REGS - 1)]); break;
-                case GP_MULK: regs[dst] = gl::mul(regs[a & (GP_MAX_REGS - 1)], 1ull << (b & 63)); break;  // b < 64 here
-                case GP_ACC: {  // acc[dst] += r[a] * imm[b], imm < 2^32: the two 32-bit halves of r[a] in separate u64 sums
-                    const uint64_t x = regs[a & (GP_MAX_REGS - 1)], c = gp.imms[b];
+                case isa::LOAD_WIRE: regs[dst] = local_wires[a * w_es]; break;
+                case isa::LOAD_CONST: regs[dst] = local_constants[(gp.num_selectors + a) * c_es]; break;
+                case isa::LOAD_PI: regs[dst] = gp.pih[a & 3]; break;
+                case isa::LOAD_IMM: regs[dst] = gp.imms[a]; break;
+                case isa::ADD: regs[dst] = gl::add(regs[a & (isa::MAX_REGS - 1)], regs[b & (isa::MAX_REGS - 1)]); break;
+                case isa::SUB: regs[dst] = gl::sub(regs[a & (isa::MAX_REGS - 1)], regs[b & (isa::MAX_REGS - 1)]); break;
+                case isa::MUL: regs[dst] = gl::mul(regs[a & (isa::MAX_REGS - 1)], regs[b & (isa::MAX_REGS - 1)]); break;
+                case isa::MULK: regs[dst] = gl::mul(regs[a & (isa::MAX_REGS - 1)], 1ull << (b & 63)); break;  // b < 64 here
+                case isa::ACC: {  // acc[dst] += r[a] * imm[b], imm < 2^32: the two 32-bit halves of r[a] in separate u64 sums
+                    const uint64_t x = regs[a & (isa::MAX_REGS - 1)], c = gp.imms[b];
                     acc_lo[dst & 3] += (x & 0xFFFFFFFFull) * c;
                     acc_hi[dst & 3] += (x >> 32) * c;
                     break;
                 }
-                case GP_ACCR:  // r[dst] = acc[a] mod p; acc[a] = 0
+                case isa::ACCR:  // r[dst] = acc[a] mod p; acc[a] = 0
                     regs[dst] = gl::fold96(acc_lo[a & 3], acc_hi[a & 3]);
                     acc_lo[a & 3] = acc_hi[a & 3] = 0;
                     break;
-                case GP_EMIT:
-                    if (k < gp.num_gate_constraints) acc[k] = gl::add(acc[k], gl::mul(filt, regs[a & (GP_MAX_REGS - 1)]));
+                case isa::EMIT:
+                    if (k < gp.num_gate_constraints) acc[k] = gl::add(acc[k], gl::mul(filt, regs[a & (isa::MAX_REGS - 1)]));
                     k++;
                     break;
                 default: break;
@@ -256,6 +256,13 @@ __global__ __launch_bounds__(128) void quotient_values_kernel(const QuotientPara
 unsigned grid_for(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }  // namespace
+
+void zh_on_coset(uint64_t shift_pow_n, uint32_t qdb, uint64_t *zh, uint64_t *zh_inv) {
+    for (uint32_t e = 0; e < (1u << qdb); e++) {
+        zh[e] = glh::add(glh::mul(shift_pow_n, glh::pow(glh::root_of_unity(qdb), e)), glh::P - 1);
+        zh_inv[e] = glh::inv(zh[e]);
+    }
+}
 
 uint32_t num_partial_products(uint32_t num_routed, uint32_t degree) { return (num_routed + degree - 1) / degree - 1; }
 
@@ -430,11 +437,7 @@ hipError_t quotient_values(const NttTables &tb, const QuotientArgs &a, uint64_t 
     const uint64_t lde_size = 1ull << (a.degree_bits + qdb);
     if (!p.has_program && !p.gate_terms && qdb <= 4) {
         ZhTable zt = {};
-        const uint64_t w = glh::root_of_unity(qdb);
-        for (uint32_t e = 0; e < (1u << qdb); e++) {  // Z_H(x) = g^n * w^(i mod 2^qdb) - 1 (zero_poly_coset.rs:20-41)
-            zt.zh[e] = glh::add(glh::mul(p.g_pow_n, glh::pow(w, e)), glh::P - 1);
-            zt.zh_inv[e] = glh::inv(zt.zh[e]);
-        }
+        zh_on_coset(p.g_pow_n, qdb, zt.zh, zt.zh_inv);
         const dim3 grid(grid_for(lde_size, 128)), block(128);
         switch (a.num_challenges) {
             case 1: hipLaunchKernelGGL(quotient_values_fast_kernel<1>, grid, block, 0, stream, p, zt); break;

@@ -1,37 +1,21 @@
 // plonk_device.h — device helpers shared by the permutation-argument kernels of plonk.hip and stark.hip: powers of the roots of
-// unity from the two-level twiddle table, the Fermat inversion chain, and the exclusive prefix product over the rows of a column
-// (block scan + scan of the block totals; the caller multiplies the two in its own finalising kernel).
+// unity and the Fermat inversion chain (point_device.h), and the exclusive prefix product over the rows of a column (block scan +
+// scan of the block totals; the caller multiplies the two in its own finalising kernel).
 // Everything sits in an unnamed namespace: each translation unit that includes this gets its own copy of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gl_field.h"
+#include "point_device.h"
 
 namespace plonky2_hip {
 
 namespace {
 
-// w_{2^log}^i through the two-level table of w_{2^24}
-__device__ __forceinline__ uint64_t root_pow(const uint64_t *twl, const uint64_t *twh, uint32_t log, uint64_t i) {
-    uint32_t e = (uint32_t)(i << (24 - log)) & 0xFFFFFFu;
-    uint64_t h = twh[e >> 12];
-    uint32_t lo = e & 4095u;
-    return lo ? gl::mul(h, twl[lo]) : h;
-}
+using pt::inverse_chain, pt::root_pow;  // point_device.h
 
 __device__ __forceinline__ uint64_t inverse(uint64_t x) { return gl::pow(x, gl::P - 2); }
-
-// x^(p-2): with e_k = x^(2^k - 1), p - 2 = (2^31 - 1) 2^33 + (2^32 - 1)
-__device__ __forceinline__ uint64_t inverse_chain(uint64_t x) {
-    auto sqn = [](uint64_t v, int k) {
-        for (int i = 0; i < k; i++) v = gl::sqr(v);
-        return v;
-    };
-    const uint64_t e2 = gl::mul(gl::sqr(x), x), e3 = gl::mul(gl::sqr(e2), x), e6 = gl::mul(sqn(e3, 3), e3), e12 = gl::mul(sqn(e6, 6), e6);
-    const uint64_t e15 = gl::mul(sqn(e12, 3), e3), e30 = gl::mul(sqn(e15, 15), e15), e31 = gl::mul(gl::sqr(e30), x), e32 = gl::mul(gl::sqr(e31), x);
-    return gl::mul(sqn(e31, 33), e32);
-}
 
 // ---- exclusive prefix product over rows ---------------------------------------------------------
 constexpr int SCAN_T = 256, SCAN_E = 4, SCAN_B = SCAN_T * SCAN_E;

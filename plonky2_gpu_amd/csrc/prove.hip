@@ -22,6 +22,7 @@
 #include "commit.h"
 #include "gate_jit.h"
 #include "gl_field.h"
+#include "jit.h"
 #include "stark.h"
 #include "stark_jit.h"
 

@@ -9,6 +9,8 @@
 
 #include "ntt.h"
 
+struct StarkJitArgs;  // stark_jit_device.h
+
 namespace plonky2_hip {
 
 constexpr uint32_t STARK_MAX_CHALLENGES = 4;  // num_challenges
@@ -71,6 +73,10 @@ struct StarkQuotientArgs {
     StarkCtlDev ctl;
     const uint64_t *ctl_challenges;
 };
+
+// What the interpreter and a compiled quotient kernel both take per proof (stark_jit_device.h), from `a`: the checks the two routes
+// share, the pointers, the coset shift, 1 / g, Z_H and its inverses, alphas and challenges mod p. `qdb`: log2_ceil(a.qdf).
+hipError_t stark_point_args(const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, ::StarkJitArgs *args, uint32_t *qdb);
 
 // out: [num_challenges][n << log2_ceil(qdf)] quotient VALUES on the coset 7 * <w>, natural order (compute_quotient_polys,
 // starky/src/prover.rs:199-319 up to the coset_ifft)

@@ -26,30 +26,28 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
-#include <cstring>
 #include <map>
 #include <mutex>
 #include <sstream>
 #include <thread>
 
-#include "gate_jit.h"
 #include "gl_field.h"
+#include "jit.h"
+#include "program_isa.h"
 #include "stark_jit_device.h"
 
 namespace plonky2_hip {
 
 namespace {
 
-const char *const GL_FIELD_SRC =
-#include "build/gl_field_src.inc"
+const char *const POINT_DEVICE_SRC =
+#include "build/point_device_src.inc"
     ;
 const char *const SJ_DEVICE_SRC =
 #include "build/stark_jit_device_src.inc"
     ;
 
-enum : uint16_t { SP_LOAD_WIRE, SP_LOAD_CONST, SP_LOAD_PI, SP_LOAD_IMM, SP_ADD, SP_SUB, SP_MUL, SP_EMIT, SP_MULK, SP_ACC, SP_ACCR,
-                  SP_LOAD_NEXT, SP_EMIT_TRANSITION, SP_EMIT_FIRST_ROW, SP_EMIT_LAST_ROW };
-constexpr uint32_t MAX_REGS = 64;
+using isa::MAX_REGS;
 const char *const KERNEL_NAME = "stark_quotient_kernel";
 
 std::string lit(uint64_t v) {
@@ -61,38 +59,39 @@ std::string lit(uint64_t v) {
 // the program (validated by stark_program_validate) as statements
 void generate_program(std::ostringstream &o, const StarkJitDesc &d) {
     const size_t n = d.instrs.size() / 4;
-    bool reg_used[MAX_REGS] = {}, acc_used[4] = {};
+    bool reg_used[MAX_REGS] = {}, acc_used[isa::MAX_ACCS] = {};
     for (size_t pc = 0; pc < n; pc++) {
-        const uint16_t op = d.instrs[4 * pc], dst = d.instrs[4 * pc + 1];
-        if (op == SP_ACC)
-            acc_used[dst & 3] = true;  // its dst names an accumulator
-        else if (op != SP_EMIT && op < SP_EMIT_TRANSITION)
-            reg_used[dst & (MAX_REGS - 1)] = true;
+        const isa::Instr in = isa::instr_at(d.instrs.data(), pc);
+        if (isa::acc_in_dst(in.op))
+            acc_used[in.dst & (isa::MAX_ACCS - 1)] = true;
+        else if (isa::writes_reg(in.op))
+            reg_used[in.dst & (MAX_REGS - 1)] = true;
     }
     for (uint32_t r = 0; r < MAX_REGS; r++)
         if (reg_used[r]) o << "  uint64_t r" << r << ";\n";
-    for (uint32_t q = 0; q < 4; q++)
+    for (uint32_t q = 0; q < isa::MAX_ACCS; q++)
         if (acc_used[q]) o << "  uint64_t a" << q << "l = 0, a" << q << "h = 0;\n";
     for (size_t pc = 0; pc < n; pc++) {
-        const uint16_t op = d.instrs[4 * pc], dst = d.instrs[4 * pc + 1] & (MAX_REGS - 1), a = d.instrs[4 * pc + 2], b = d.instrs[4 * pc + 3];
+        const isa::Instr in = isa::instr_at(d.instrs.data(), pc);
+        const uint16_t op = in.op, dst = in.dst & (MAX_REGS - 1), a = in.a, b = in.b;
         const uint32_t ra = a & (MAX_REGS - 1), rb = b & (MAX_REGS - 1);
         switch (op) {
-            case SP_LOAD_WIRE: o << "  r" << dst << " = q.local[" << a << " * p.stride];\n"; break;
-            case SP_LOAD_NEXT: o << "  r" << dst << " = q.next[" << a << " * p.stride];\n"; break;
-            case SP_LOAD_PI: o << "  r" << dst << " = p.pis[" << a << "];\n"; break;
-            case SP_LOAD_IMM: o << "  r" << dst << " = " << lit(d.imms[a]) << ";\n"; break;
-            case SP_ADD: o << "  r" << dst << " = gl::add(r" << ra << ", r" << rb << ");\n"; break;
-            case SP_SUB: o << "  r" << dst << " = gl::sub(r" << ra << ", r" << rb << ");\n"; break;
-            case SP_MUL: o << "  r" << dst << " = gl::mul(r" << ra << ", r" << rb << ");\n"; break;
-            case SP_MULK: o << "  r" << dst << " = gl::mul(r" << ra << ", " << lit(1ull << (b & 63)) << ");\n"; break;
-            case SP_ACC: o << "  sj::acc(a" << (dst & 3) << "l, a" << (dst & 3) << "h, r" << ra << ", " << d.imms[b] << "u);\n"; break;
-            case SP_ACCR:
+            case isa::LOAD_WIRE: o << "  r" << dst << " = q.local[" << a << " * p.stride];\n"; break;
+            case isa::LOAD_NEXT: o << "  r" << dst << " = q.next[" << a << " * p.stride];\n"; break;
+            case isa::LOAD_PI: o << "  r" << dst << " = p.pis[" << a << "];\n"; break;
+            case isa::LOAD_IMM: o << "  r" << dst << " = " << lit(d.imms[a]) << ";\n"; break;
+            case isa::ADD: o << "  r" << dst << " = gl::add(r" << ra << ", r" << rb << ");\n"; break;
+            case isa::SUB: o << "  r" << dst << " = gl::sub(r" << ra << ", r" << rb << ");\n"; break;
+            case isa::MUL: o << "  r" << dst << " = gl::mul(r" << ra << ", r" << rb << ");\n"; break;
+            case isa::MULK: o << "  r" << dst << " = gl::mul(r" << ra << ", " << lit(1ull << (b & 63)) << ");\n"; break;
+            case isa::ACC: o << "  sj::acc(a" << (dst & 3) << "l, a" << (dst & 3) << "h, r" << ra << ", " << d.imms[b] << "u);\n"; break;
+            case isa::ACCR:
                 o << "  r" << dst << " = gl::fold96(a" << (a & 3) << "l, a" << (a & 3) << "h); a" << (a & 3) << "l = 0; a" << (a & 3) << "h = 0;\n";
                 break;
-            case SP_EMIT: o << "  sj::constraint(sums, p, r" << ra << ");\n"; break;
-            case SP_EMIT_TRANSITION: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.z_last));\n"; break;
-            case SP_EMIT_FIRST_ROW: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.l_first));\n"; break;
-            case SP_EMIT_LAST_ROW: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.l_last));\n"; break;
+            case isa::EMIT: o << "  sj::constraint(sums, p, r" << ra << ");\n"; break;
+            case isa::EMIT_TRANSITION: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.z_last));\n"; break;
+            case isa::EMIT_FIRST_ROW: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.l_first));\n"; break;
+            case isa::EMIT_LAST_ROW: o << "  sj::constraint(sums, p, gl::mul(r" << ra << ", q.l_last));\n"; break;
             default: break;  // refused by stark_program_validate
         }
     }
@@ -162,21 +161,11 @@ void generate_ctl_checks(std::ostringstream &o, const StarkJitDesc &d, uint32_t 
     }
 }
 
-// a code object that hipModuleLoadData may be given: an ELF whose section header table lies inside the buffer (a file cut short
-// loses it: the table is the last thing in the file)
-bool code_object_whole(const std::vector<char> &code) {
-    if (code.size() < 64 || memcmp(code.data(), "\177ELF", 4) != 0) return false;
-    uint64_t shoff = 0;
-    uint16_t shentsize = 0, shnum = 0;
-    memcpy(&shoff, code.data() + 0x28, 8), memcpy(&shentsize, code.data() + 0x3A, 2), memcpy(&shnum, code.data() + 0x3C, 2);
-    return shoff >= 64 && shnum != 0 && shoff <= code.size() && (uint64_t)shentsize * shnum <= code.size() - shoff;
-}
-
 }  // namespace
 
 std::string stark_jit_source(const StarkJitDesc &d) {
     std::ostringstream o;
-    o << "#define GL_JIT 1\n" << GL_FIELD_SRC << "\n" << SJ_DEVICE_SRC << "\n";
+    o << "#define GL_JIT 1\n" << jit_field_source() << "\n" << POINT_DEVICE_SRC << "\n" << SJ_DEVICE_SRC << "\n";
     o << "#define NCH " << d.num_challenges << "\n#define QDB " << glh::log2_ceil(d.qdf) << "\n";
     o << "extern \"C\" __global__ __launch_bounds__(128) void " << KERNEL_NAME << "(const StarkJitArgs p) {\n"
          "  sj::Point q;\n  if (!sj::head<QDB>(p, q)) return;\n  uint64_t sums[NCH];\n  for (int c = 0; c < NCH; c++) sums[c] = 0;\n";
@@ -287,37 +276,11 @@ const char *stark_jit_kernel_source(const StarkJitKernel *k) { return k->source.
 
 hipError_t stark_jit_launch(const StarkJitKernel *kc, const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream) {
     StarkJitKernel *k = const_cast<StarkJitKernel *>(kc);  // the modules per device are the object's own
-    const uint32_t qdb = glh::log2_ceil(a.qdf);
-    if (a.num_challenges == 0 || a.num_challenges > STARK_MAX_CHALLENGES || a.qdf == 0 || a.qdf > STARK_MAX_QDF || qdb > a.rate_bits ||
-        a.degree_bits == 0 || a.degree_bits + a.rate_bits > 24 || a.column_stride < (1ull << (a.degree_bits + a.rate_bits)) || !a.alphas)
+    if (a.degree_bits == 0 || a.num_challenges != k->num_challenges || a.qdf != k->qdf || a.pairs.num_pairs != k->num_pairs || a.ctl.num_zs != k->num_ctl_zs)
         return hipErrorInvalidValue;
-    if (a.num_challenges != k->num_challenges || a.qdf != k->qdf || a.pairs.num_pairs != k->num_pairs || a.ctl.num_zs != k->num_ctl_zs)
-        return hipErrorInvalidValue;
-    StarkJitArgs p = {};
-    p.pis = a.public_inputs, p.trace = a.trace_lde, p.zs = a.zs_lde, p.twl = tb.twl, p.twh = tb.twh, p.out = out, p.stride = a.column_stride;
-    p.degree_bits = a.degree_bits;
-    if (k->num_pairs) {
-        if (!a.zs_lde || !a.challenges) return hipErrorInvalidValue;
-        for (uint32_t s = 0; s < a.qdf * a.num_challenges; s++) {
-            p.perm_beta[s] = a.challenges[2 * s] % glh::P;
-            p.perm_gamma[s] = a.challenges[2 * s + 1] % glh::P;
-        }
-    }
-    if (k->num_ctl_zs) {
-        if (!a.zs_lde || !a.ctl_challenges) return hipErrorInvalidValue;
-        for (uint32_t c = 0; c < a.num_challenges; c++) {
-            p.ctl_beta[c] = a.ctl_challenges[2 * c] % glh::P;
-            p.ctl_gamma[c] = a.ctl_challenges[2 * c + 1] % glh::P;
-        }
-    }
-    p.shift = 7;
-    p.g_inv = glh::inv(glh::root_of_unity(a.degree_bits));
-    for (uint32_t c = 0; c < a.num_challenges; c++) p.alpha[c] = a.alphas[c] % glh::P;
-    const uint64_t g_pow_n = glh::pow(p.shift, 1ull << a.degree_bits), w = glh::root_of_unity(qdb);
-    for (uint32_t e = 0; e < (1u << qdb); e++) {  // Z_H(x) = shift^n * w^(i mod 2^qdb) - 1 (zero_poly_coset.rs:20-41)
-        p.zh[e] = glh::add(glh::mul(g_pow_n, glh::pow(w, e)), glh::P - 1);
-        p.zh_inv[e] = glh::inv(p.zh[e]);
-    }
+    StarkJitArgs p;
+    uint32_t qdb = 0;
+    if (hipError_t e = stark_point_args(tb, a, out, &p, &qdb); e != hipSuccess) return e;
     hipFunction_t fn;
     if (hipError_t e = k->function(&fn); e != hipSuccess) return e;
     const uint64_t size = 1ull << (a.degree_bits + qdb);
