@@ -750,6 +750,46 @@ const char *gl_stark_tables_kernel_source(const void *tables, uint32_t table);
 GlError gl_stark_precompile(uint32_t hasher, const GlStarkDesc *desc);
 GlError gl_stark_tables_precompile(uint32_t hasher, const GlStarkTablesDesc *desc);
 
+/* ---- ... as several kernel units (for long programs) ------------------------------------------------
+ * hiprtc's compile time is superlinear in the length of one kernel's straight-line body, so a program of tens of thousands of
+ * instructions (the Keccak-f table's 47 227) cannot be compiled as one kernel in reasonable time. The *_units calls cut the
+ * description into UNITS of at most max_unit_instrs instructions each and compile one kernel per unit; the kernels run in order
+ * on the call's stream and hand the constraint consumer's running sums on through the call's own output buffer, so the quotient
+ * is still the interpreter's bit for bit. max_unit_instrs = 0: the library's default cap (1000; DESIGN.md 3.7.3 has the
+ * measurements behind it).
+ *   * The program is cut by gl_stark_split_program's rule (below). The permutation checks and a table's CTL checks follow the
+ *     program in the consumer's order; a check counts the field operations it generates; they go into the last program unit
+ *     while they fit under the cap and into further units otherwise. One CTL Z's pair of constraints is never cut.
+ *   * One stark_<hash>.hsaco + .hip per distinct unit source in the kernel cache; all units (of all tables) compile side by
+ *     side on at most 8 threads. Failure is all or nothing: the handle stays interpreted and usable.
+ *   * A handle compiled in units is used by several host threads on several contexts at once like any other.
+ * gl_stark_compile / gl_stark_tables_compile / gl_stark_precompile / gl_stark_tables_precompile keep producing ONE unit with the
+ * sources and cache names they always had. On a handle that is already compiled every compile call is a no-op.
+ * gl_stark_kernel_units: 0 while interpreted. gl_stark_kernel_unit_source: NULL unless compiled or beyond the units;
+ * gl_stark_kernel_source is unit 0's. */
+GlError gl_stark_compile_units(void *stark, uint32_t max_unit_instrs, void *ctx);
+GlError gl_stark_tables_compile_units(void *tables, uint32_t max_unit_instrs, void *ctx);
+GlError gl_stark_precompile_units(uint32_t hasher, const GlStarkDesc *desc, uint32_t max_unit_instrs);
+GlError gl_stark_tables_precompile_units(uint32_t hasher, const GlStarkTablesDesc *desc, uint32_t max_unit_instrs);
+int gl_stark_kernel_units(const void *stark);
+int gl_stark_tables_kernel_units(const void *tables, uint32_t table);
+const char *gl_stark_kernel_unit_source(const void *stark, uint32_t unit);
+const char *gl_stark_tables_kernel_unit_source(const void *tables, uint32_t table, uint32_t unit);
+/* The device-free splitter of desc's program (only the program, its immediates, num_columns and num_public_inputs are read and
+ * validated as gl_stark_create validates them; max_unit_instrs = 0: the default cap). Unit k holds a contiguous run of the
+ * program's EMIT* instructions, the runs partition all EMITs in order, and its body is the backward slice of its EMITs: every
+ * instruction an EMIT transitively reads through "the latest write of that register", every ACC since the previous ACCR of an
+ * accumulator whose ACCR is kept, in the original order with the original register numbers. A value live across a cut is
+ * computed again in every unit that reads it. A unit grows constraint by constraint while its slice has at most max_unit_instrs
+ * instructions; one constraint whose slice alone is longer is a unit of its own. max_unit_instrs >= num_instrs: one unit, the
+ * input word for word. Every unit is a program gl_stark_create accepts with desc's immediates, columns and public inputs.
+ * ONE result for all units, laid out and released as gl_keccak_table_program's (gl_gate_programs_free), with a descriptor per
+ * unit: instrs = the units' programs one behind the other, immediates = desc's (shared, indices unchanged), num_gates = the
+ * number of units, gates[k] = {row = k, selector_index = 0, group_start / group_end = the unit's EMITs are numbers group_start
+ * .. group_end - 1 of the program's, prog_start, prog_len = the unit's instructions in instrs}, num_gate_constraints = the
+ * program's EMITs. */
+GlError gl_stark_split_program(const GlStarkDesc *desc, uint32_t max_unit_instrs, GlGatePrograms *out);
+
 /* ---------------------------------------------------------------------------------------------
  * The lookup columns of a trace: the Halo2-style lookup argument of the reference's STARKs (evm/src/lookup.rs, used by its memory
  * table, memory_stark.rs:147, and by system_zero/src/lookup.rs). A lookup is four trace columns: the inputs, the table, and the

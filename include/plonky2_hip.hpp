@@ -349,6 +349,17 @@ class Stark {
     }
     // gl_stark_precompile: validate, generate and compile into the kernel cache without a device (a build machine's step)
     static void precompile(const GlStarkDesc &desc, Hasher hasher = Hasher::Poseidon) { check(gl_stark_precompile((uint32_t)hasher, &desc)); }
+    // gl_stark_compile_units / gl_stark_precompile_units: the same as several kernels of at most max_unit_instrs instructions
+    // that run in order (0: the library's default cap) — what a long program needs to compile in reasonable time
+    void compile_units(const Context &ctx, uint32_t max_unit_instrs = 0) { check(gl_stark_compile_units(ptr_, max_unit_instrs, ctx.get())); }
+    uint32_t num_units() const { return (uint32_t)gl_stark_kernel_units(ptr_); }  // 0 while interpreted
+    std::string unit_source(uint32_t unit) const {
+        const char *src = gl_stark_kernel_unit_source(ptr_, unit);
+        return src ? src : "";
+    }
+    static void precompile_units(const GlStarkDesc &desc, uint32_t max_unit_instrs = 0, Hasher hasher = Hasher::Poseidon) {
+        check(gl_stark_precompile_units((uint32_t)hasher, &desc, max_unit_instrs));
+    }
 
   private:
     void *ptr_ = nullptr;
@@ -388,6 +399,16 @@ class StarkTables {
     }
     static void precompile(const GlStarkTablesDesc &desc, Hasher hasher = Hasher::Poseidon) {
         check(gl_stark_tables_precompile((uint32_t)hasher, &desc));
+    }
+    // gl_stark_tables_compile_units / gl_stark_tables_precompile_units: every table in units, as Stark::compile_units
+    void compile_units(const Context &ctx, uint32_t max_unit_instrs = 0) { check(gl_stark_tables_compile_units(ptr_, max_unit_instrs, ctx.get())); }
+    uint32_t num_units(uint32_t table) const { return (uint32_t)gl_stark_tables_kernel_units(ptr_, table); }
+    std::string unit_source(uint32_t table, uint32_t unit) const {
+        const char *src = gl_stark_tables_kernel_unit_source(ptr_, table, unit);
+        return src ? src : "";
+    }
+    static void precompile_units(const GlStarkTablesDesc &desc, uint32_t max_unit_instrs = 0, Hasher hasher = Hasher::Poseidon) {
+        check(gl_stark_tables_precompile_units((uint32_t)hasher, &desc, max_unit_instrs));
     }
 
   private:
@@ -446,6 +467,24 @@ inline MemoryTableProgram memory_table_program() {
     out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
     out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
     out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
+// gl_stark_split_program: the unit programs gl_stark_compile_units cuts desc's program into (device-free). Every unit is a
+// program of its own over desc's immediates; its EMITs are numbers emit_start .. emit_end - 1 of the program's.
+struct StarkProgramUnit {
+    std::vector<GlGateInstr> instrs;
+    uint32_t emit_start = 0, emit_end = 0;
+};
+inline std::vector<StarkProgramUnit> stark_split_program(const GlStarkDesc &desc, uint32_t max_unit_instrs = 0) {
+    GlGatePrograms p;
+    check(gl_stark_split_program(&desc, max_unit_instrs, &p));
+    std::vector<StarkProgramUnit> out(p.num_gates);
+    for (uint32_t k = 0; k < p.num_gates; k++) {
+        out[k].instrs.assign(p.instrs + p.gates[k].prog_start, p.instrs + p.gates[k].prog_start + p.gates[k].prog_len);
+        out[k].emit_start = p.gates[k].group_start, out[k].emit_end = p.gates[k].group_end;
+    }
     gl_gate_programs_free(&p);
     return out;
 }

@@ -257,6 +257,15 @@ SIGNATURES = {
     "gl_stark_tables_kernel_source": (ctypes.c_char_p, [_vp, _u32]),
     "gl_stark_precompile": (GlError, [_u32, ctypes.POINTER(GlStarkDesc)]),
     "gl_stark_tables_precompile": (GlError, [_u32, ctypes.POINTER(GlStarkTablesDesc)]),
+    "gl_stark_compile_units": (GlError, [_vp, _u32, _vp]),
+    "gl_stark_tables_compile_units": (GlError, [_vp, _u32, _vp]),
+    "gl_stark_precompile_units": (GlError, [_u32, ctypes.POINTER(GlStarkDesc), _u32]),
+    "gl_stark_tables_precompile_units": (GlError, [_u32, ctypes.POINTER(GlStarkTablesDesc), _u32]),
+    "gl_stark_kernel_units": (ctypes.c_int, [_vp]),
+    "gl_stark_tables_kernel_units": (ctypes.c_int, [_vp, _u32]),
+    "gl_stark_kernel_unit_source": (ctypes.c_char_p, [_vp, _u32]),
+    "gl_stark_tables_kernel_unit_source": (ctypes.c_char_p, [_vp, _u32, _u32]),
+    "gl_stark_split_program": (GlError, [ctypes.POINTER(GlStarkDesc), _u32, _vp]),
     "gl_lookup_scratch_bytes": (_u64, [_u64]),
     "gl_sort_canonical": (GlError, [_vp, _vp, _u64, _vp, _vp]),
     "gl_lookup_permuted_cols": (GlError, [_vp, _vp, _u64, _vp, _vp, _vp, _vp]),

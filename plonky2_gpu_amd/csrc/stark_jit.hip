@@ -18,6 +18,16 @@
 // Everything that varies per proof is a kernel argument BY VALUE (StarkJitArgs): no __constant__ table is written in front of a
 // launch, so one compiled handle is used by several host threads on several contexts at once without taking turns.
 //
+// UNITS (stark_jit_units): hiprtc's instruction selection is superlinear in the length of one basic block, so a long description is
+// cut into several kernels the way gate_jit.hip cuts a circuit's gates. The program is cut by stark_program_split (stark_split.h),
+// the permutation and CTL checks behind it by the field operations they generate. Unit 0 starts the consumer's sums at 0, every
+// later unit loads them from p.out[c * size + q.i], every unit but the last stores them there raw, only the last runs sj::tail;
+// the units run in order on the call's stream and a thread reads and writes only its own elements. That is the same Horner chain
+// over the same operands — a 64-bit word stored and loaded is the same word — so the stored quotient is the interpreter's bit for
+// bit by the argument for one kernel; there is no new one. Every unit calls sj::head in full: what a unit does not read of the
+// Point (the inversion and root_pow in a unit of plain EMITs, zh_inv in every unit but the last) is dead code to the compiler,
+// and the text in front of the generated body stays the single kernel's.
+//
 // Occupancy: __launch_bounds__(128) as the interpreter, and no waves-per-SIMD attribute — the program's live values decide the
 // registers (at most 64 program registers = 128 VGPRs plus the running sums and what the scheduler hoists), the compiler may take
 // up to 512 and never spills into scratch; a fixed occupancy would trade that for spills on the programs that need the registers.
@@ -35,6 +45,7 @@
 #include "jit.h"
 #include "program_isa.h"
 #include "stark_jit_device.h"
+#include "stark_split.h"
 
 namespace plonky2_hip {
 
@@ -57,11 +68,11 @@ std::string lit(uint64_t v) {
 }
 
 // the program (validated by stark_program_validate) as statements
-void generate_program(std::ostringstream &o, const StarkJitDesc &d) {
-    const size_t n = d.instrs.size() / 4;
+void generate_program(std::ostringstream &o, const StarkJitDesc &d, const std::vector<uint16_t> &instrs) {
+    const size_t n = instrs.size() / 4;
     bool reg_used[MAX_REGS] = {}, acc_used[isa::MAX_ACCS] = {};
     for (size_t pc = 0; pc < n; pc++) {
-        const isa::Instr in = isa::instr_at(d.instrs.data(), pc);
+        const isa::Instr in = isa::instr_at(instrs.data(), pc);
         if (isa::acc_in_dst(in.op))
             acc_used[in.dst & (isa::MAX_ACCS - 1)] = true;
         else if (isa::writes_reg(in.op))
@@ -72,7 +83,7 @@ void generate_program(std::ostringstream &o, const StarkJitDesc &d) {
     for (uint32_t q = 0; q < isa::MAX_ACCS; q++)
         if (acc_used[q]) o << "  uint64_t a" << q << "l = 0, a" << q << "h = 0;\n";
     for (size_t pc = 0; pc < n; pc++) {
-        const isa::Instr in = isa::instr_at(d.instrs.data(), pc);
+        const isa::Instr in = isa::instr_at(instrs.data(), pc);
         const uint16_t op = in.op, dst = in.dst & (MAX_REGS - 1), a = in.a, b = in.b;
         const uint32_t ra = a & (MAX_REGS - 1), rb = b & (MAX_REGS - 1);
         switch (op) {
@@ -99,13 +110,14 @@ void generate_program(std::ostringstream &o, const StarkJitDesc &d) {
 
 // eval_permutation_checks (permutation.rs:284-322): Z(1) = 1 for every Z, then per batch Z(g x) prod rhs = Z(x) prod lhs; batch
 // z holds the instances f = z * qdf + k, instance f = (pair f / num_challenges, challenge f % num_challenges) under SET k
-uint32_t generate_permutation_checks(std::ostringstream &o, const StarkJitDesc &d) {
-    const uint32_t np = d.num_pairs(), nch = d.num_challenges;
-    if (!np) return 0;
-    const uint32_t instances = np * nch, num_zs = stark_num_zs(np, nch, d.qdf);
-    for (uint32_t z = 0; z < num_zs; z++)
+void generate_permutation_first_rows(std::ostringstream &o, uint32_t z0, uint32_t z1) {
+    for (uint32_t z = z0; z < z1; z++)
         o << "  sj::constraint(sums, p, gl::mul(gl::sub(p.zs[" << z << " * p.stride + q.t], 1), q.l_first));\n";
-    for (uint32_t z = 0; z < num_zs; z++) {
+}
+
+void generate_permutation_batches(std::ostringstream &o, const StarkJitDesc &d, uint32_t z0, uint32_t z1) {
+    const uint32_t nch = d.num_challenges, instances = d.num_pairs() * nch;
+    for (uint32_t z = z0; z < z1; z++) {
         o << "  {\n    uint64_t lhs = 1, rhs = 1;\n";
         for (uint32_t k = 0; k < d.qdf; k++) {
             const uint32_t f = z * d.qdf + k;
@@ -121,8 +133,9 @@ uint32_t generate_permutation_checks(std::ostringstream &o, const StarkJitDesc &
         o << "    sj::constraint(sums, p, gl::sub(gl::mul(p.zs[" << z << " * p.stride + q.t_next], rhs), gl::mul(p.zs[" << z
           << " * p.stride + q.t], lhs)));\n  }\n";
     }
-    return num_zs;
 }
+
+uint32_t num_permutation_zs(const StarkJitDesc &d) { return d.num_pairs() ? stark_num_zs(d.num_pairs(), d.num_challenges, d.qdf) : 0; }
 
 // Column::eval (cross_table_lookup.rs:100-119) of CTL column k at `row` as an expression statement into `name`
 void generate_ctl_column(std::ostringstream &o, const StarkJitDesc &d, const std::string &name, uint32_t k, const char *row) {
@@ -134,8 +147,9 @@ void generate_ctl_column(std::ostringstream &o, const StarkJitDesc &d, const std
 // eval_cross_table_lookup_checks (evm/src/cross_table_lookup.rs:421-450), the CTL Zs behind the permutation Zs: with
 // select(f, x) = f x + 1 - f, Z(1) = select(filter, combine) on the first row and Z(g x) = Z(x) select(filter', combine') on every
 // row but the last
-void generate_ctl_checks(std::ostringstream &o, const StarkJitDesc &d, uint32_t num_perm_zs) {
-    for (uint32_t z = 0; z < d.ctl_zs.size() / 2; z++) {
+void generate_ctl_checks(std::ostringstream &o, const StarkJitDesc &d, uint32_t z0, uint32_t z1) {
+    const uint32_t num_perm_zs = num_permutation_zs(d);
+    for (uint32_t z = z0; z < z1; z++) {
         const uint32_t tw = d.ctl_zs[2 * z], c = d.ctl_zs[2 * z + 1], filter = d.twc_filter[tw];
         o << "  {\n    const uint64_t beta = p.ctl_beta[" << c << "], gamma = p.ctl_gamma[" << c << "];\n    uint64_t sel[2];\n";
         for (int side = 0; side < 2; side++) {
@@ -161,20 +175,71 @@ void generate_ctl_checks(std::ostringstream &o, const StarkJitDesc &d, uint32_t 
     }
 }
 
+// The checks behind the program in the consumer's order, as items that a cut may fall between: the permutation Zs' first-row
+// checks, their batch checks, then the CTL Zs — one CTL Z's pair of constraints is one item.
+uint32_t num_check_items(const StarkJitDesc &d) { return 2 * num_permutation_zs(d) + (uint32_t)d.ctl_zs.size() / 2; }
+
+void generate_checks(std::ostringstream &o, const StarkJitDesc &d, uint32_t i0, uint32_t i1) {
+    const uint32_t nz = num_permutation_zs(d);
+    auto clip = [&](uint32_t base, uint32_t i) { return std::min(std::max(i, base), num_check_items(d)) - base; };
+    generate_permutation_first_rows(o, clip(0, i0), std::min(clip(0, i1), nz));
+    generate_permutation_batches(o, d, std::min(clip(nz, i0), nz), std::min(clip(nz, i1), nz));
+    generate_ctl_checks(o, d, clip(2 * nz, i0), clip(2 * nz, i1));
+}
+
+// what an item costs against the cap: the field operations and consumer calls of its generated text, the unit in which an
+// instruction of the program costs one
+uint32_t check_item_cost(const StarkJitDesc &d, uint32_t i) {
+    std::ostringstream o;
+    generate_checks(o, d, i, i + 1);
+    const std::string text = o.str();
+    uint32_t cost = 0;
+    for (size_t at = 0; (at = text.find("::", at)) != std::string::npos; at += 2) cost++;
+    return cost;
+}
+
 }  // namespace
 
-std::string stark_jit_source(const StarkJitDesc &d) {
+std::vector<StarkJitUnit> stark_jit_units(const StarkJitDesc &d, uint32_t max_unit_instrs) {
+    std::vector<StarkJitUnit> units;
+    const uint32_t items = num_check_items(d);
+    if (max_unit_instrs == STARK_JIT_ONE_UNIT) {
+        units.push_back(StarkJitUnit{d.instrs, 0, items});
+        return units;
+    }
+    for (StarkProgramUnit &u : stark_program_split(d.instrs.data(), (uint32_t)(d.instrs.size() / 4), max_unit_instrs))
+        units.push_back(StarkJitUnit{std::move(u.instrs), 0, 0});
+    // the checks go into the last program unit while they fit and into further units otherwise; an item above the cap is a unit
+    uint64_t used = units.back().instrs.size() / 4;
+    for (uint32_t i = 0; i < items; i++) {
+        const uint32_t cost = check_item_cost(d, i);
+        const bool empty = units.back().instrs.empty() && units.back().check_start == units.back().check_end;
+        if (used + cost > max_unit_instrs && !empty) {
+            units.push_back(StarkJitUnit{{}, i, i});
+            used = 0;
+        }
+        if (units.back().check_start == units.back().check_end) units.back().check_start = i;
+        units.back().check_end = i + 1;
+        used += cost;
+    }
+    return units;
+}
+
+std::string stark_jit_unit_source(const StarkJitDesc &d, const StarkJitUnit &u, bool first, bool last) {
     std::ostringstream o;
     o << "#define GL_JIT 1\n" << jit_field_source() << "\n" << POINT_DEVICE_SRC << "\n" << SJ_DEVICE_SRC << "\n";
     o << "#define NCH " << d.num_challenges << "\n#define QDB " << glh::log2_ceil(d.qdf) << "\n";
     o << "extern \"C\" __global__ __launch_bounds__(128) void " << KERNEL_NAME << "(const StarkJitArgs p) {\n"
-         "  sj::Point q;\n  if (!sj::head<QDB>(p, q)) return;\n  uint64_t sums[NCH];\n  for (int c = 0; c < NCH; c++) sums[c] = 0;\n";
-    generate_program(o, d);
-    const uint32_t num_perm_zs = generate_permutation_checks(o, d);
-    generate_ctl_checks(o, d, num_perm_zs);
-    o << "  sj::tail(sums, p, q);\n}\n";
+         "  sj::Point q;\n  if (!sj::head<QDB>(p, q)) return;\n  uint64_t sums[NCH];\n";
+    // the running sums between units live in the call's own out, raw, at the elements the tail will store to
+    o << (first ? "  for (int c = 0; c < NCH; c++) sums[c] = 0;\n" : "  for (int c = 0; c < NCH; c++) sums[c] = p.out[(uint64_t)c * q.size + q.i];\n");
+    generate_program(o, d, u.instrs);
+    generate_checks(o, d, u.check_start, u.check_end);
+    o << (last ? "  sj::tail(sums, p, q);\n}\n" : "  for (int c = 0; c < NCH; c++) p.out[(uint64_t)c * q.size + q.i] = sums[c];\n}\n");
     return o.str();
 }
+
+std::string stark_jit_source(const StarkJitDesc &d) { return stark_jit_unit_source(d, stark_jit_units(d, STARK_JIT_ONE_UNIT)[0], true, true); }
 
 bool stark_jit_compile_sources(const std::vector<std::string> &sources, std::vector<std::vector<char>> *codes, uint32_t *written, std::string *error) {
     const std::string dir = jit_cache_dir();
@@ -215,49 +280,56 @@ bool stark_jit_compile_sources(const std::vector<std::string> &sources, std::vec
 }
 
 struct StarkJitKernel {
-    std::string source;
-    std::vector<char> code;
+    std::vector<std::string> sources;      // per unit, in launch order
+    std::vector<std::vector<char>> codes;
     uint32_t num_challenges = 0, qdf = 0, num_pairs = 0, num_ctl_zs = 0;
-    // a module per device the handle has launched on
+    // a module per unit per device the handle has launched on
     struct Loaded {
-        hipModule_t module;
-        hipFunction_t fn;
+        std::vector<hipModule_t> modules;
+        std::vector<hipFunction_t> fns;
     };
     std::mutex mu;
     std::map<int, Loaded> loaded;
-    hipError_t function(hipFunction_t *fn) {
+    hipError_t functions(const std::vector<hipFunction_t> **fns) {
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
         std::lock_guard<std::mutex> lock(mu);
         auto it = loaded.find(dev);
         if (it == loaded.end()) {
-            Loaded l{nullptr, nullptr};
-            e = hipModuleLoadData(&l.module, code.data());
-            if (e == hipSuccess) e = hipModuleGetFunction(&l.fn, l.module, KERNEL_NAME);
-            if (e != hipSuccess) {
-                if (l.module) (void)hipModuleUnload(l.module);
-                return e;
+            Loaded l;
+            for (const std::vector<char> &code : codes) {
+                hipModule_t module = nullptr;
+                hipFunction_t fn = nullptr;
+                e = hipModuleLoadData(&module, code.data());
+                if (module) l.modules.push_back(module);
+                if (e == hipSuccess) e = hipModuleGetFunction(&fn, module, KERNEL_NAME);
+                if (e != hipSuccess) {  // all units or none
+                    for (hipModule_t m : l.modules) (void)hipModuleUnload(m);
+                    return e;
+                }
+                l.fns.push_back(fn);
             }
-            it = loaded.emplace(dev, l).first;
+            it = loaded.emplace(dev, std::move(l)).first;
         }
-        *fn = it->second.fn;
+        *fns = &it->second.fns;  // the map's nodes stay where they are
         return hipSuccess;
     }
 };
 
-StarkJitKernel *stark_jit_load(const StarkJitDesc &d, const std::string &source, std::vector<char> &&code, std::string *error) {
-    if (!code_object_whole(code)) {
-        const std::string path = jit_cache_path(jit_cache_dir(), source, "stark_");
-        *error = "loading the compiled STARK quotient kernel: the code object is no whole ELF file" +
-                 (path.empty() ? std::string() : " (a damaged cache entry? " + path + ".hsaco)");
-        return nullptr;
-    }
+StarkJitKernel *stark_jit_load(const StarkJitDesc &d, const std::vector<std::string> &sources, std::vector<std::vector<char>> &&codes, std::string *error) {
+    for (size_t u = 0; u < codes.size(); u++)
+        if (!code_object_whole(codes[u])) {
+            const std::string path = jit_cache_path(jit_cache_dir(), sources[u], "stark_");
+            *error = "loading the compiled STARK quotient kernel: the code object is no whole ELF file" +
+                     (path.empty() ? std::string() : " (a damaged cache entry? " + path + ".hsaco)");
+            return nullptr;
+        }
     StarkJitKernel *k = new StarkJitKernel();
-    k->source = source, k->code = std::move(code);
+    k->sources = sources, k->codes = std::move(codes);
     k->num_challenges = d.num_challenges, k->qdf = d.qdf, k->num_pairs = d.num_pairs(), k->num_ctl_zs = (uint32_t)d.ctl_zs.size() / 2;
-    hipFunction_t fn;
-    if (hipError_t e = k->function(&fn); e != hipSuccess) {
+    const std::vector<hipFunction_t> *fns;
+    if (hipError_t e = k->functions(&fns); e != hipSuccess) {
         (void)hipGetLastError();
         *error = std::string("loading the compiled STARK quotient kernel: ") + hipGetErrorString(e);
         delete k;
@@ -268,11 +340,14 @@ StarkJitKernel *stark_jit_load(const StarkJitDesc &d, const std::string &source,
 
 void stark_jit_destroy(StarkJitKernel *k) {
     if (!k) return;
-    for (auto &kv : k->loaded) (void)hipModuleUnload(kv.second.module);
+    for (auto &kv : k->loaded)
+        for (hipModule_t m : kv.second.modules) (void)hipModuleUnload(m);
     delete k;
 }
 
-const char *stark_jit_kernel_source(const StarkJitKernel *k) { return k->source.c_str(); }
+uint32_t stark_jit_kernel_units(const StarkJitKernel *k) { return (uint32_t)k->sources.size(); }
+
+const char *stark_jit_kernel_source(const StarkJitKernel *k, uint32_t unit) { return unit < k->sources.size() ? k->sources[unit].c_str() : nullptr; }
 
 hipError_t stark_jit_launch(const StarkJitKernel *kc, const NttTables &tb, const StarkQuotientArgs &a, uint64_t *out, hipStream_t stream) {
     StarkJitKernel *k = const_cast<StarkJitKernel *>(kc);  // the modules per device are the object's own
@@ -281,11 +356,14 @@ hipError_t stark_jit_launch(const StarkJitKernel *kc, const NttTables &tb, const
     StarkJitArgs p;
     uint32_t qdb = 0;
     if (hipError_t e = stark_point_args(tb, a, out, &p, &qdb); e != hipSuccess) return e;
-    hipFunction_t fn;
-    if (hipError_t e = k->function(&fn); e != hipSuccess) return e;
+    const std::vector<hipFunction_t> *fns;
+    if (hipError_t e = k->functions(&fns); e != hipSuccess) return e;
     const uint64_t size = 1ull << (a.degree_bits + qdb);
     void *args[] = {&p};
-    return hipModuleLaunchKernel(fn, (unsigned)((size + 127) / 128), 1, 1, 128, 1, 1, 0, stream, args, nullptr);
+    // the units in order on one stream: unit k + 1 reads the sums unit k stored, each thread its own
+    for (hipFunction_t fn : *fns)
+        if (hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((size + 127) / 128), 1, 1, 128, 1, 1, 0, stream, args, nullptr); e != hipSuccess) return e;
+    return hipSuccess;
 }
 
 }  // namespace plonky2_hip

@@ -121,9 +121,10 @@ def _c_stark_desc(desc):
 
 
 class NativeStark:
-    """gl_stark_create: the handle of one STARK on one device; prove_bytes() = gl_stark_prove. `compiled`: compile() at once."""
+    """gl_stark_create: the handle of one STARK on one device; prove_bytes() = gl_stark_prove. `compiled`: compile(unit_instrs)
+    at once."""
 
-    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, compiled=False):
+    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, compiled=False, unit_instrs=None):
         self.ctx, self.desc, self.hasher = ctx, desc, _lib.hasher_id(hasher)
         self.ptr = None
         d, _keep = _c_stark_desc(desc)
@@ -131,13 +132,18 @@ class NativeStark:
         _lib.call("gl_stark_create", self.hasher, ctypes.byref(d), ctypes.byref(h), ctx.ptr)
         self.ptr = h.value
         if compiled:
-            self.compile()
+            self.compile(unit_instrs)
 
-    def compile(self):
+    def compile(self, unit_instrs=None):
         """gl_stark_compile: from now on the quotient runs the kernel generated from this STARK's description instead of the
         interpreter — the same values. Only between proofs; a second call is a no-op; on failure (Plonky2HipError with the
-        compiler's log) the handle stays interpreted and usable."""
-        _lib.call("gl_stark_compile", self.ptr, self.ctx.ptr)
+        compiler's log) the handle stays interpreted and usable. `unit_instrs` (gl_stark_compile_units): cut the description into
+        kernels of at most that many instructions that run in order — what a long program needs to compile in reasonable time;
+        0 takes the library's default cap, None is the single kernel."""
+        if unit_instrs is None:
+            _lib.call("gl_stark_compile", self.ptr, self.ctx.ptr)
+        else:
+            _lib.call("gl_stark_compile_units", self.ptr, int(unit_instrs), self.ctx.ptr)
 
     @property
     def is_compiled(self):
@@ -148,6 +154,18 @@ class NativeStark:
         """the generated HIP source, or None unless compiled"""
         src = _lib.load().gl_stark_kernel_source(self.ptr)
         return None if src is None else src.decode()
+
+    @property
+    def num_units(self):
+        """the number of kernels the quotient runs; 0 while interpreted"""
+        return int(_lib.load().gl_stark_kernel_units(self.ptr))
+
+    @property
+    def unit_sources(self):
+        """the generated HIP source of every unit in launch order, or None unless compiled"""
+        if not self.is_compiled:
+            return None
+        return [_lib.load().gl_stark_kernel_unit_source(self.ptr, u).decode() for u in range(self.num_units)]
 
     def prove_bytes(self, trace, public_inputs, timing=None, ctx=None):
         """`trace`: host [num_columns][n] value columns or a DeviceBuffer; `ctx`: another context of the handle's device (several host
@@ -454,9 +472,9 @@ def _tables_c_desc(desc, flat):
 
 class NativeStarkTables:
     """gl_stark_tables_create: the handle of several STARKs and their cross-table lookups on one device. `flat`: the arrays of
-    desc.flatten(), for callers that build them themselves. `compiled`: compile() at once."""
+    desc.flatten(), for callers that build them themselves. `compiled`: compile(unit_instrs) at once."""
 
-    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, flat=None, compiled=False):
+    def __init__(self, ctx, desc, hasher=_lib.GL_HASHER_POSEIDON, flat=None, compiled=False, unit_instrs=None):
         self.ctx, self.desc, self.hasher = ctx, desc, _lib.hasher_id(hasher)
         self.ptr = None
         d, _keep = _tables_c_desc(desc, flat if flat is not None else desc.flatten())
@@ -464,12 +482,16 @@ class NativeStarkTables:
         _lib.call("gl_stark_tables_create", self.hasher, ctypes.byref(d), ctypes.byref(h), ctx.ptr)
         self.ptr = h.value
         if compiled:
-            self.compile()
+            self.compile(unit_instrs)
 
-    def compile(self):
+    def compile(self, unit_instrs=None):
         """gl_stark_tables_compile: one generated quotient kernel per table (program, permutation checks and the table's CTL
-        checks), as NativeStark.compile; all tables or none."""
-        _lib.call("gl_stark_tables_compile", self.ptr, self.ctx.ptr)
+        checks), as NativeStark.compile; all tables or none. `unit_instrs` (gl_stark_tables_compile_units): every table in units
+        of at most that many instructions, 0 for the library's default cap."""
+        if unit_instrs is None:
+            _lib.call("gl_stark_tables_compile", self.ptr, self.ctx.ptr)
+        else:
+            _lib.call("gl_stark_tables_compile_units", self.ptr, int(unit_instrs), self.ctx.ptr)
 
     @property
     def is_compiled(self):
@@ -481,6 +503,18 @@ class NativeStarkTables:
         if not self.is_compiled:
             return None
         return [_lib.load().gl_stark_tables_kernel_source(self.ptr, k).decode() for k in range(len(self.desc.tables))]
+
+    @property
+    def num_units(self):
+        """per table the number of kernels its quotient runs; 0 while interpreted"""
+        return [int(_lib.load().gl_stark_tables_kernel_units(self.ptr, k)) for k in range(len(self.desc.tables))]
+
+    @property
+    def unit_sources(self):
+        """per table the generated HIP source of every unit in launch order, or None unless compiled"""
+        if not self.is_compiled:
+            return None
+        return [[_lib.load().gl_stark_tables_kernel_unit_source(self.ptr, k, u).decode() for u in range(n)] for k, n in enumerate(self.num_units)]
 
     def prove_bytes(self, traces, timing=None, ctx=None):
         """`traces`: per table host [num_columns][n] value columns or a DeviceBuffer; `timing`: a list that receives one dict of stage
@@ -544,16 +578,32 @@ class NativeStarkTables:
             pass
 
 
-def precompile(desc, hasher=_lib.GL_HASHER_POSEIDON):
+def precompile(desc, hasher=_lib.GL_HASHER_POSEIDON, unit_instrs=None):
     """gl_stark_precompile / gl_stark_tables_precompile of a StarkDesc / StarkTablesDesc: validate as the handle's constructor
     does, generate the quotient kernel(s) and compile them into the kernel cache. Needs no device: what a build machine runs so
-    that compile() finds its kernels."""
-    if isinstance(desc, StarkTablesDesc):
-        d, _keep = _tables_c_desc(desc, desc.flatten())
-        _lib.call("gl_stark_tables_precompile", _lib.hasher_id(hasher), ctypes.byref(d))
+    that compile() finds its kernels. `unit_instrs` as compile()'s (gl_stark_precompile_units / gl_stark_tables_precompile_units)."""
+    tables = isinstance(desc, StarkTablesDesc)
+    d, _keep = _tables_c_desc(desc, desc.flatten()) if tables else _c_stark_desc(desc)
+    name = "gl_stark_tables_precompile" if tables else "gl_stark_precompile"
+    if unit_instrs is None:
+        _lib.call(name, _lib.hasher_id(hasher), ctypes.byref(d))
     else:
-        d, _keep = _c_stark_desc(desc)
-        _lib.call("gl_stark_precompile", _lib.hasher_id(hasher), ctypes.byref(d))
+        _lib.call(name + "_units", _lib.hasher_id(hasher), ctypes.byref(d), int(unit_instrs))
+
+
+def split_program(desc, unit_instrs):
+    """gl_stark_split_program: the unit programs compile(unit_instrs) cuts a StarkDesc's program into, as a list of
+    (instrs [k][4] uint16, (first, one past the last) of the program's EMITs the unit yields). Every unit is a program of its own
+    over desc.immediates; a value that lives across a cut is computed again in each unit that reads it. Needs no device."""
+    d, _keep = _c_stark_desc(desc)
+    out = _lib.GlGatePrograms()
+    _lib.call("gl_stark_split_program", ctypes.byref(d), int(unit_instrs), ctypes.byref(out))
+    try:
+        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
+        gates = np.ctypeslib.as_array(ctypes.cast(out.gates, ctypes.POINTER(ctypes.c_uint32)), shape=(out.num_gates, 6)).copy()
+        return [(instrs[int(g[4]):int(g[4]) + int(g[5])], (int(g[2]), int(g[3]))) for g in gates]
+    finally:
+        _lib.load().gl_gate_programs_free(ctypes.byref(out))
 
 
 # ---------------------------------------------------------------- wire format (include/plonky2_hip.h, gl_stark_tables_prove)

@@ -33,7 +33,16 @@ come back from the compiler library in about 11 ms. The shapes are fibonacci, wi
              against the next row, per word the 32-bit recomposition by ACC / ACCR, every constraint under the filter. Timed
              through gl_stark_quotient_polys on random words (that needs no valid trace), compiled against interpreted.
 
-  python tools/bench_stark_prove.py --compiled [--shapes fibonacci,wide,dense,ctl] [--reps 7] [--compiled-out profiles/stark_compiled.json]"""
+  python tools/bench_stark_prove.py --compiled [--shapes fibonacci,wide,dense,ctl] [--reps 7] [--compiled-out profiles/stark_compiled.json]
+
+--unit-instrs N (with --compiled) adds to the shapes timed through gl_stark_quotient_polys a THIRD handle, compiled in units of at
+most N instructions (gl_stark_compile_units; 0: the library's default cap): `cut` beside `compiled`, with its own cold and warm
+compile_ms and its number of units — what cutting costs at run time and saves at compile time. Besides dense that is
+
+  fuzz4000   the 4 000-instruction program of tests/stark_fuzz.py (description 11: 4 challenges, 3 public inputs) without its
+             permutation pairs: the longest single basic block the suite compiles
+
+  python tools/bench_stark_prove.py --compiled --unit-instrs 0 --shapes dense,fuzz4000 [--min-bits 16] [--max-bits 20]"""
 import argparse
 import ctypes
 import json
@@ -281,9 +290,9 @@ def _stats(ms):
     return {"median_ms": round(float(np.median(ms)), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
 
 
-def _compile_ms(make_handle):
+def _compile_ms(make_handle, unit_instrs=None):
     """(cold, warm): gl_stark_compile / gl_stark_tables_compile of a fresh handle with an empty temporary kernel cache, and of
-    another fresh handle with the cache the first one filled"""
+    another fresh handle with the cache the first one filled; `unit_instrs`: in units (gl_stark_compile_units)"""
     cache = tempfile.mkdtemp(prefix="stark_kernel_cache_")
     saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
     os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
@@ -292,7 +301,7 @@ def _compile_ms(make_handle):
         for _ in range(2):
             h = make_handle()
             t0 = time.perf_counter()
-            h.compile()
+            h.compile(unit_instrs)
             out.append(round((time.perf_counter() - t0) * 1e3, 1))
             h.close()
         return out
@@ -336,40 +345,60 @@ def measure_compiled(ctx, make, degree_bits, reps, hasher="poseidon"):
     return res
 
 
-def measure_dense(ctx, degree_bits, reps, hasher="poseidon"):
+def fuzz4000_desc(degree_bits):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stark_fuzz as sf
+
+    case = sf.fuzz_case(sf.LENGTHS.index(4000))
+    s = case["stark"]
+    return pstark.StarkDesc(degree_bits, s.num_columns, s.num_public_inputs, s.constraint_degree, case["num_challenges"],
+                            fast_config_fri_params(degree_bits), s.instrs, s.immediates, [])
+
+
+def measure_dense(ctx, degree_bits, reps, hasher="poseidon", make_desc=None, unit_instrs=None):
     """gl_stark_quotient_polys on random words in place of the trace's LDE: the call ends synchronised and includes the upload of the
-    (empty) public inputs and the coset iNTT of the two quotient columns, the same on both sides"""
-    desc = dense_desc(degree_bits)
+    public inputs and the coset iNTT of the quotient columns, the same on every side. `unit_instrs`: a third handle, compiled in
+    units of at most that many instructions"""
+    desc = (make_desc or dense_desc)(degree_bits)
     n_ext, size = 1 << (degree_bits + 1), 1 << (degree_bits + desc.quotient_degree_bits)
     rng = np.random.default_rng(degree_bits)
     d_lde = pg.DeviceBuffer(ctx, desc.num_columns * n_ext)
     for c in range(desc.num_columns):
         _lib.call("gl_memcpy_h2d", d_lde.at(c * n_ext), rng.integers(0, P, size=n_ext, dtype=np.uint64), 8 * n_ext, ctx.ptr)
-    alphas = np.ascontiguousarray(rng.integers(0, P, size=2, dtype=np.uint64))
-    pis = np.zeros(1, dtype=np.uint64)
+    alphas = np.ascontiguousarray(rng.integers(0, P, size=desc.num_challenges, dtype=np.uint64))
+    pis = np.ascontiguousarray(rng.integers(0, P, size=max(1, desc.num_public_inputs), dtype=np.uint64))
     cold, warm = _compile_ms(lambda: pg.NativeStark(ctx, desc, hasher))
     handles = [pg.NativeStark(ctx, desc, hasher), pg.NativeStark(ctx, desc, hasher, compiled=True)]
-    outs = [pg.DeviceBuffer(ctx, 2 * size) for _ in handles]
+    names = ["interpreted", "compiled"]
+    if unit_instrs is not None:
+        cut_cold, cut_warm = _compile_ms(lambda: pg.NativeStark(ctx, desc, hasher), unit_instrs)
+        handles.append(pg.NativeStark(ctx, desc, hasher, compiled=True, unit_instrs=unit_instrs))
+        names.append("cut")
+    outs = [pg.DeviceBuffer(ctx, desc.num_challenges * size) for _ in handles]
 
     def call(ns, d_q):
         _lib.call("gl_stark_quotient_polys", ns.ptr, d_lde.ptr, None, n_ext, alphas, None, pis, d_q.ptr, ctx.ptr)
 
     for ns, d_q in zip(handles, outs):
         call(ns, d_q)
-    if not (outs[0].download() == outs[1].download()).all():
-        raise SystemExit("bench_stark_prove: the compiled handle's quotient differs from the interpreted handle's")
-    ms = ([], [])
+    if not all((outs[0].download() == d_q.download()).all() for d_q in outs[1:]):
+        raise SystemExit("bench_stark_prove: a compiled handle's quotient differs from the interpreted handle's")
+    ms = tuple([] for _ in handles)
     for _ in range(reps):
         for k, (ns, d_q) in enumerate(zip(handles, outs)):
             t0 = time.perf_counter()
             call(ns, d_q)
             ms[k].append((time.perf_counter() - t0) * 1e3)
+    res = {"columns": desc.num_columns, "instructions": int(desc.instrs.shape[0]), "compile_ms": {"cold": cold, "warm": warm}}
+    for k, name in enumerate(names):
+        res[name] = dict(_stats(ms[k]), call="gl_stark_quotient_polys")
+    if unit_instrs is not None:
+        res["cut"].update(unit_instrs=unit_instrs, units=handles[2].num_units, compile_ms={"cold": cut_cold, "warm": cut_warm})
     for ns in handles:
         ns.close()
     for b in outs + [d_lde]:
         b.free()
-    return {"columns": desc.num_columns, "instructions": int(desc.instrs.shape[0]), "compile_ms": {"cold": cold, "warm": warm},
-            "interpreted": dict(_stats(ms[0]), call="gl_stark_quotient_polys"), "compiled": dict(_stats(ms[1]), call="gl_stark_quotient_polys")}
+    return res
 
 
 def measure_ctl_compiled(ctx, reps, hasher="poseidon"):
@@ -400,7 +429,10 @@ def main_compiled(a, ctx, res):
             continue
         res[shape] = {}
         for bits in range(a.min_bits, a.max_bits + 1):
-            res[shape]["2^%d" % bits] = measure_dense(ctx, bits, a.reps) if shape == "dense" else measure_compiled(ctx, makers[shape], bits, a.reps)
+            if shape in ("dense", "fuzz4000"):
+                res[shape]["2^%d" % bits] = measure_dense(ctx, bits, a.reps, make_desc=fuzz4000_desc if shape == "fuzz4000" else None, unit_instrs=a.unit_instrs)
+            else:
+                res[shape]["2^%d" % bits] = measure_compiled(ctx, makers[shape], bits, a.reps)
             print(shape, bits, json.dumps(res[shape]["2^%d" % bits]), file=sys.stderr, flush=True)
     ctx.close()
     line = json.dumps(res)
@@ -418,6 +450,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--shapes", default=None, help="default: fibonacci,wide; with --compiled: fibonacci,wide,dense,ctl")
     ap.add_argument("--compiled", action="store_true", help="compiled quotient kernels against the interpreter, in one run")
+    ap.add_argument("--unit-instrs", type=int, default=None, help="with --compiled: also a handle compiled in units of at most N (0: the default cap)")
     ap.add_argument("--compiled-out", default=os.path.join(ROOT, "profiles", "stark_compiled.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stark_prove.json"))
     ap.add_argument("--ctl-out", default=os.path.join(ROOT, "profiles", "stark_ctl_prove.json"))
