@@ -903,6 +903,55 @@ GlError gl_debug_memory_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, 
                                        void *d_scratch, float *h_ms, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The logic table: the reference's LogicStark (evm/src/logic.rs), the looked table of ctl_logic — what the CPU table's AND / OR /
+ * XOR and the Keccak sponge's byte XORs look into — 523 columns, one row per operation on two 256-bit words — with its trace
+ * built in HBM from a compact operation list and its constraints emitted natively, so that gl_stark_prove /
+ * gl_stark_tables_prove prove it without the trace ever visiting the host.
+ * gl_logic_table_trace = generate_trace_rows (logic.rs:157-176). d_ops: [num_ops][17] words of 64 bits in device memory, one
+ * record per operation: word 0 the operator, given as the index of its flag column (0 = AND, 1 = OR, 2 = XOR); words 1 .. 8 the
+ * eight 32-bit limbs of input0, least significant first; words 9 .. 16 the eight 32-bit limbs of input1. The result is not part
+ * of the record: the device computes it. LIMITS, checked on the device: the operator is 0, 1 or 2, every limb is below 2^32.
+ * d_trace receives [523][pitch trace_stride] value columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. Columns
+ * (logic.rs:28-52): IS_AND 0, IS_OR 1, IS_XOR 2, the bits of INPUT0 3 .. 258, least significant first, the bits of INPUT1
+ * 259 .. 514, the eight 32-bit limbs of RESULT 515 .. 522. CONTRACT: row k < num_ops is Operation::into_row of record k (the
+ * list order is the row order); rows num_ops .. n are all zero. With degree_bits = log2(next_power_of_two(max(num_ops, 1))),
+ * at least 1, the trace is the reference's; a larger degree_bits is allowed and plays generate_trace_rows' min_rows. Every word
+ * of the 523 columns is written on every row and is canonical — a flag, a bit or a 32-bit limb —: the buffer need not be
+ * zeroed; the words between n and trace_stride are left untouched. num_ops == 0 is allowed (d_ops may then be NULL) and gives
+ * an all-padding trace. PROTOCOL: a validation kernel runs first on ctx->stream; the host then reads one status word from
+ * d_scratch — the call's ONE host wait —; the rows are enqueued behind it and the call returns without waiting for them. With
+ * num_ops == 0 nothing is validated and the call does not wait. Nothing is allocated: d_scratch is
+ * GL_LOGIC_TABLE_SCRATCH_BYTES bytes in device memory, 16-byte aligned, and holds nothing between calls.
+ * Refused with GL_E_INVALID and a message, the trace untouched — for the data: an operator word that is not 0, 1 or 2, a limb
+ * of 2^32 or more (the message names the lowest record index at fault and which of the two it was; the operator where that
+ * record has both) — and before anything is launched: degree_bits outside 1 ..= 23 (what gl_stark_create takes for constraints
+ * of degree 3), num_ops > n, trace_stride < n, a NULL pointer (other than d_ops with num_ops == 0), d_scratch not 16-byte
+ * aligned, d_ops, d_trace and d_scratch overlapping one another.
+ * gl_logic_table_program = eval_packed_generic (logic.rs:182-231) as ONE STARK program in the encoding of GlStarkDesc.h_instrs,
+ * 520 constraints of degree 3 in the reference's order (the order decides the powers of alpha and so the proof's bytes): the 256
+ * bit checks bit (bit - 1) of INPUT0, the 256 of INPUT1, then per result limb i = 0 .. 7
+ * RESULT[i] - (sum_coeff (x + y) + and_coeff x_land_y) with sum_coeff = IS_OR + IS_XOR, and_coeff = IS_AND - IS_OR - 2 IS_XOR,
+ * x and y the limb's 32 bits of the two inputs recomposed and x_land_y the weighted sum of their 32 products. The
+ * recompositions and the weighted sum go through ACC in blocks of 16 weights that keep its overflow contract; the program stays
+ * within 64 registers and 4 accumulators. Device-free; the result is laid out and released as gl_keccak_table_program's. The
+ * table has no public inputs and no permutation pairs; its cross-table lookup (logic.rs:54-68) has 27 columns — the three flags
+ * as single columns, eight combinations sum_j 2^j column(3 + 32 i + j) over j < 32 for INPUT0, eight such over
+ * column(259 + 32 i + j) for INPUT1, the eight RESULT columns 515 .. 522 — and the combination IS_AND + IS_OR + IS_XOR as filter.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_LOGIC_TABLE_COLUMNS 523
+#define GL_LOGIC_TABLE_OP_WORDS 17
+#define GL_LOGIC_TABLE_SCRATCH_BYTES 16
+GlError gl_logic_table_trace(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                             void *d_scratch, void *ctx);
+GlError gl_logic_table_program(GlGatePrograms *out);
+/* Measurement hook: the rows of gl_logic_table_trace alone, without the validation and its wait, at a chosen store width —
+ * rows_per_thread 1: one row per thread, 8 bytes per lane and column store; 2: two adjacent rows per thread, 16 bytes per lane,
+ * which needs d_trace 16-byte aligned and an even trace_stride. The records must be within the limits above: an operator
+ * outside them gives a row without flag and result, a limb is cut to 32 bits. Same argument refusals as gl_logic_table_trace. */
+GlError gl_debug_logic_table_fill(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                                  uint32_t rows_per_thread, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

@@ -471,6 +471,27 @@ inline MemoryTableProgram memory_table_program() {
     return out;
 }
 
+// The logic table (plonky2_hip.h "The logic table"). logic_table_trace: d_ops [num_ops][17] records (operator, the limbs of the
+// two inputs) -> d_trace [523][trace_stride] with 2^degree_bits rows, list order = row order, zero rows behind. d_scratch:
+// GL_LOGIC_TABLE_SCRATCH_BYTES bytes in HBM, 16-byte aligned. The call waits once, for the validation (not at all with
+// num_ops == 0); the trace is complete on the context's stream before a prove() of the same context reads it.
+// logic_table_program: its constraints (constraint_degree 3, no public inputs, no pairs).
+inline void logic_table_trace(const Context &ctx, const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                              uint64_t trace_stride, void *d_scratch) {
+    check(gl_logic_table_trace(d_ops, num_ops, degree_bits, d_trace, trace_stride, d_scratch, ctx.get()));
+}
+using LogicTableProgram = KeccakTableProgram;  // instructions, immediates and the number of constraints
+inline LogicTableProgram logic_table_program() {
+    GlGatePrograms p;
+    check(gl_logic_table_program(&p));
+    LogicTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 // gl_stark_split_program: the unit programs gl_stark_compile_units cuts desc's program into (device-free). Every unit is a
 // program of its own over desc's immediates; its EMITs are numbers emit_start .. emit_end - 1 of the program's.
 struct StarkProgramUnit {

@@ -1253,6 +1253,59 @@ Program program(ImmediatePool &pool) {
 
 }  // namespace memory_table
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's logic table (evm/src/logic.rs:182-231) as ONE STARK program:
+// plonky2_gpu_amd/logic_table.py program(), call for call (tests/test_logic_table_ref.py holds the two against each other word
+// for word).
+namespace logic_table {
+
+// logic.rs:28-52
+enum { IS_AND = 0, IS_OR = 1, IS_XOR = 2, INPUT0 = 3, INPUT1 = 259, RESULT = 515, VAL_BITS = 256, PACKED_LEN = 8 };
+
+Program program(ImmediatePool &pool) {
+    keccak_table::Asm a(&pool);
+    // all bits are indeed bits
+    for (int start : {INPUT0, INPUT1})
+        for (int i = 0; i < VAL_BITS; i++) {
+            a.release();
+            const int bit = a.local(start + i);
+            const int one = a.imm(1);
+            const int t = a.sub(bit, one);
+            a.emit(a.mul(bit, t));
+        }
+    // RESULT[i] = sum_coeff (x + y) + and_coeff (x AND y) on the limb's 32 bits
+    for (int i = 0; i < PACKED_LEN; i++) {
+        a.release();
+        const int x = a.limb([&](int z) { return a.local(INPUT0 + z); }, 32 * i);
+        const int y = a.limb([&](int z) { return a.local(INPUT1 + z); }, 32 * i);
+        const int x_land_y = a.limb(
+            [&](int z) {
+                const int x_bit = a.local(INPUT0 + z);
+                const int y_bit = a.local(INPUT1 + z);
+                a.mul(x_bit, y_bit, x_bit);
+                a.free1(y_bit);
+                return x_bit;
+            },
+            32 * i);
+        const int is_and = a.local(IS_AND);
+        const int is_or = a.local(IS_OR);
+        const int is_xor = a.local(IS_XOR);
+        const int sum_coeff = a.add(is_or, is_xor);
+        const int and_coeff = a.sub(is_and, is_or);
+        a.mulk(is_xor, 1, is_xor);
+        a.sub(and_coeff, is_xor, and_coeff);
+        a.add(x, y, x);
+        a.mul(sum_coeff, x, x);
+        a.mul(and_coeff, x_land_y, x_land_y);
+        a.add(x, x_land_y, x);
+        const int result = a.local(RESULT + i);
+        a.emit(a.sub(result, x));
+    }
+    return a.instrs;
+}
+
+}  // namespace logic_table
+
 // a table's STARK program as a GlGatePrograms without gate descriptors; num_gate_constraints counts its EMITs of every kind
 GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePool &), GlGatePrograms *out) {
     if (!out) return emit_error(name + ": null pointer");
@@ -1288,6 +1341,8 @@ GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePo
 extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) { return emit_table_program("gl_keccak_table_program", keccak_table::program, out); }
 
 extern "C" GlError gl_memory_table_program(GlGatePrograms *out) { return emit_table_program("gl_memory_table_program", memory_table::program, out); }
+
+extern "C" GlError gl_logic_table_program(GlGatePrograms *out) { return emit_table_program("gl_logic_table_program", logic_table::program, out); }
 
 extern "C" GlError gl_gate_programs_emit(const GlGateSpec *gates, uint32_t num_gates, const uint32_t *group_bounds, uint32_t num_selectors,
                                          GlGatePrograms *out) {
