@@ -129,7 +129,7 @@ public:
     DeviceCall &operator=(const DeviceCall &) = delete;
 };
 
-// makes the device of `ctx` current and returns its tables and workspace (the prover's host logic, prove.hip)
+// makes the device of `ctx` current and returns its tables and workspace (the provers' host logic, prove.hip and stark_prove.hip)
 hipError_t ctx_tables(void *ctx, const NttTables **out);
 
 }  // namespace plonky2_hip

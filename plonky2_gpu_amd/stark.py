@@ -1,4 +1,4 @@
-"""STARKs: starky's prove() on the device (gl_stark_create / gl_stark_prove, csrc/prove.hip and csrc/stark.hip).
+"""STARKs: starky's prove() on the device (gl_stark_create / gl_stark_prove, csrc/stark_prove.hip and csrc/stark.hip).
 
 A STARK is described by its shape, its permutation pairs and ONE register program for all its constraints — what a host derives from
 `Stark::eval_packed_generic` (starky/src/stark.rs) the way the gate programs are derived from `eval_unfiltered_*`. The program uses

@@ -292,3 +292,68 @@ def test_prove_many_keeps_several_proofs_in_flight_and_every_proof_is_the_one_ma
         nc.close()
         for c in others:
             c.close()
+
+
+@pytest.mark.gpu
+def test_a_proof_from_a_fresh_thread_runs_on_the_device_of_its_context(gpu):
+    """A context on device 1, used from a thread whose current device is still 0 (every fresh host thread's is): gl_prove,
+    gl_stark_prove and gl_stark_tables_prove make the context's device current before they allocate anything (ProofSession,
+    csrc/prove_common.h), so each returns the bytes the same call returns on device 0 from the main thread."""
+    import ctl_instances as ci
+    import plonky2_gpu_amd as pg
+    import stark_instances as si
+    from plonk_instance import make_circuit
+
+    if pg.load().gl_device_count() < 2:
+        pytest.skip("needs two devices")
+    circuit, wires, pis = make_circuit(4, seed=661)
+    circuit = dict(circuit, circuit_digest=None)
+    flat = np.ascontiguousarray(np.array(wires, dtype=np.uint64).reshape(-1))
+    stark_desc = si.A.desc(3, 2, si.fri_params(rate_bits=1, arity_bits=(1, 2)))
+    trace, stark_pis = si.A.make_trace(3, seed=3)
+    trace = np.ascontiguousarray(np.array(trace, dtype=np.uint64).reshape(-1))
+    tables_desc = ci.system().desc(ci.DEGREE_BITS, 2, ci.fri_params())
+    traces = [np.ascontiguousarray(np.array(t, dtype=np.uint64).reshape(-1)) for t in ci.make_traces(0)]
+
+    def handles(ctx):  # on the calling thread's current device, which is the context's
+        return (pg.NativeCircuit(ctx, circuit), pg.NativeStark(ctx, stark_desc), pg.NativeStarkTables(ctx, tables_desc),
+                pg.DeviceBuffer.from_host(ctx, flat), pg.DeviceBuffer.from_host(ctx, trace), [pg.DeviceBuffer.from_host(ctx, t) for t in traces])
+
+    def prove(h, ctx):
+        nc, ns, nt, d_wires, d_trace, d_traces = h
+        return [nc.prove_bytes(d_wires, pis, ctx=ctx), ns.prove_bytes(d_trace, stark_pis, ctx=ctx), nt.prove_bytes(d_traces, ctx=ctx)]
+
+    def close(h):
+        for x in h[:3]:
+            x.close()
+        for b in [h[3], h[4]] + h[5]:
+            b.free()
+
+    h0 = handles(gpu)
+    expect = prove(h0, gpu)
+    close(h0)
+    hip = _hip()
+    assert hip.hipSetDevice(1) == 0
+    other = pg.Context(1)
+    try:
+        h1 = handles(other)
+        other.synchronize()
+        assert hip.hipSetDevice(0) == 0
+        got, errors = [], []
+
+        def work():
+            try:
+                got.extend(prove(h1, other))
+            except Exception as e:  # noqa: BLE001
+                errors.append(e)
+
+        t = threading.Thread(target=work)
+        t.start()
+        t.join()
+        assert not errors, errors
+        assert got == expect
+        assert hip.hipSetDevice(1) == 0
+        close(h1)
+    finally:
+        hip.hipSetDevice(0)
+        other.close()
