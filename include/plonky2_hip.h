@@ -952,6 +952,84 @@ GlError gl_debug_logic_table_fill(const uint64_t *d_ops, uint64_t num_ops, uint3
                                   uint32_t rows_per_thread, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The Keccak sponge table: the reference's KeccakSpongeStark (evm/src/keccak_sponge/), the table that ties the three above
+ * together — the only looker of ctl_keccak, five of the lookers of ctl_logic, 136 of the lookers of ctl_memory and the looked
+ * table of ctl_keccak_sponge — 414 columns, len / 136 + 1 rows per hashed byte string. A list of byte strings goes in once; the
+ * sponge's trace and the records the other three trace calls take come out in HBM.
+ * gl_keccak_sponge_table_trace = generate_trace_rows (keccak_sponge_stark.rs:190-347), bit for bit. d_ops: [num_ops][5] words
+ * of 64 bits in device memory, one record per KeccakSpongeOp: context, segment, virt (the base address), timestamp, len.
+ * d_bytes: the inputs concatenated in list order, one uint8_t each, no alignment promised; may be NULL when every len is 0.
+ * d_ops may be NULL when num_ops == 0, which gives an all-padding trace. LIMITS, checked on the device: every record word is
+ * below 2^32, virt + len <= 2^32, the sum of all len is below 2^32; num_ops <= 2^30.
+ * d_trace receives [414][pitch trace_stride] value columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. Columns
+ * (columns.rs:15-60): is_full_input_block 0, is_final_block 1, context 2, segment 3, virt 4, timestamp 5, len 6,
+ * already_absorbed_bytes 7, is_final_input_len 8 .. 143, original_rate_u32s 144 .. 177, original_capacity_u32s 178 .. 193,
+ * block_bytes 194 .. 329, xored_rate_u32s 330 .. 363, updated_state_u32s 364 .. 413. ROWS: operation k takes len_k / 136 + 1
+ * consecutive rows, in list order: its full-block rows, then the final row, padded by pad10*1 (0x01 behind the input, 0x80 in
+ * byte 135; a remainder of 135 bytes puts 0x81 in one byte). State limb 2 j / 2 j + 1 is the low / high half of Keccak lane j
+ * (keccak_util.rs:6-18). The rows behind the operations are all zero. Every word of the 414 columns is written on every row and
+ * is canonical: the buffer need not be zeroed; the words between n and trace_stride are left untouched.
+ * ROW COUNT: rows = sum_k (len_k / 136 + 1) depends on the data and is returned in *h_rows; d_trace == NULL asks for the count
+ * alone (trace_stride and d_bytes are not read; degree_bits still sizes the scratch). The reference sizes its trace as
+ * next_power_of_two(max(num_ops, min_rows)) and silently drops whatever does not fit (.take(num_rows)), which cuts an operation in
+ * the middle; this call REFUSES rows > n and names the count needed. CONTRACT: with n >= rows the trace is the reference's for
+ * that n (for a min_rows with next_power_of_two(max(num_ops, min_rows)) == n).
+ * PROTOCOL, as gl_memory_table_trace's: validation, the per-operation row and byte counts and their exclusive prefix sums run on
+ * ctx->stream; the host then reads the row count and the status words — the call's ONE host wait —; the fill is enqueued
+ * behind it and the call returns without waiting for it. With num_ops == 0 nothing is counted and the call does not wait. The
+ * fill is two kernels: one lane per operation walks the operation's blocks (absorb, Keccak-f, next block; the only serial part)
+ * and writes the 100 state columns; one lane per row writes the other 314. Nothing is allocated: d_scratch is
+ * gl_keccak_sponge_table_scratch_bytes(num_ops, degree_bits) bytes in device memory, 16-byte aligned (32 + 8 (n + 2 num_ops)
+ * bytes and a little), and holds nothing between calls; 0 is returned for arguments out of range.
+ * Refused with GL_E_INVALID and a message that names the reason, the trace untouched — for the data: a record outside the
+ * limits (the message names the LOWEST record at fault and its fault; *h_rows is 0); rows > n (*h_rows says what is needed);
+ * d_bytes NULL although a len is not 0; d_trace overlapping the bytes the operations name — and before anything is launched:
+ * degree_bits outside 1 ..= 23 (what gl_stark_create takes for constraints of degree 3), num_ops > 2^30, trace_stride < n, a NULL
+ * pointer other than d_trace, d_bytes and (with num_ops == 0) d_ops, d_scratch not 16-byte aligned, d_ops, d_trace and d_scratch
+ * overlapping one another. Keeping d_bytes apart from d_scratch is the caller's: its extent is known on the device alone.
+ * gl_keccak_sponge_table_ops reads rows 0 .. rows of a finished trace (rows as *h_rows gave it) and writes what
+ * keccak_sponge_log (witness/util.rs:196-250) pushes for the other tables; any output may be NULL:
+ *   d_keccak_inputs [rows][25]: the state behind the XOR — lane j is limbs 2 j, 2 j + 1 of xored_rate_u32s ++
+ *     original_capacity_u32s —, what push_keccak_bytes receives: the input of gl_keccak_table_trace;
+ *   d_logic_ops [5 rows][17]: record 5 r + i is XOR (2), limbs 8 i .. of original_rate_u32s, the little-endian u32s of
+ *     block_bytes[32 i ..], both zero-padded to eight limbs (record 4 carries two): xor_into_sponge's order, the input of
+ *     gl_logic_table_trace;
+ *   d_memory_ops [sum of len][14]: one read per input byte (padding bytes get none), by operation, then by address: FILTER 1,
+ *     TIMESTAMP = timestamp, IS_READ 1, context, segment, virt + offset, the byte, seven zeros: the input of
+ *     gl_memory_table_trace. A row's first record stands at the exclusive prefix sum of the rows' byte counts (136 for a full
+ *     row, len - already_absorbed_bytes for a final one), computed on the device.
+ * Runs on ctx->stream, waits for nothing, allocates nothing; d_scratch is gl_keccak_sponge_table_scratch_bytes(k, degree_bits)
+ * bytes for any k (the trace call's scratch serves). Refused before anything is launched: NULL d_trace or d_scratch, degree_bits,
+ * rows > n, trace_stride < n, alignment, an output overlapping the trace, the scratch or (the two of known size) each other.
+ * gl_keccak_sponge_table_program: the table's constraints as ONE STARK program in the encoding of GlStarkDesc.h_instrs. The
+ * reference's eval_packed_generic for this table is a list of TODOs (keccak_sponge_stark.rs:363-377); gl_stark_create refuses a
+ * program without an EMIT, so the program is THAT LIST WRITTEN OUT — the reference's to-do list, NOT a soundness claim (nothing
+ * here ties xored_rate_u32s to the block, for example: that is the logic lookup's job). 435 constraints of degree <= 3, in this
+ * order, with F = is_full_input_block, L = is_final_block, d = is_final_input_len: F (F - 1), L (L - 1), F L; d[i] (d[i] - 1),
+ * i < 136; sum_i d[i] - L; on the first row original_rate_u32s[j], original_capacity_u32s[j], already_absorbed_bytes (51); as
+ * transitions L next.original_rate_u32s[j], L next.original_capacity_u32s[j], L next.already_absorbed_bytes (51); F (next.x - x)
+ * for x = context, segment, virt, timestamp, len; F (next.original_rate_u32s[j] - updated_state_u32s[j]), j < 34, and
+ * F (next.original_capacity_u32s[j] - updated_state_u32s[34 + j]), j < 16; F (next.already_absorbed_bytes -
+ * already_absorbed_bytes - 136); (1 - F - L) (next.F + next.L); and plain again d[i] (len - already_absorbed_bytes - i), i < 136.
+ * The TODO's "before_rate_bits, block_bits" name columns this layout does not have: nothing is emitted for them. Device-free;
+ * the result is laid out and released as gl_keccak_table_program's. constraint_degree 3, no public inputs, no permutation pairs.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_KECCAK_SPONGE_TABLE_COLUMNS 414
+#define GL_KECCAK_SPONGE_TABLE_OP_WORDS 5
+uint64_t gl_keccak_sponge_table_scratch_bytes(uint64_t num_ops, uint32_t degree_bits);
+GlError gl_keccak_sponge_table_trace(const uint64_t *d_ops, uint64_t num_ops, const uint8_t *d_bytes, uint32_t degree_bits, uint64_t *d_trace,
+                                     uint64_t trace_stride, void *d_scratch, uint64_t *h_rows, void *ctx);
+GlError gl_keccak_sponge_table_ops(const uint64_t *d_trace, uint64_t trace_stride, uint32_t degree_bits, uint64_t rows, uint64_t *d_keccak_inputs,
+                                   uint64_t *d_logic_ops, uint64_t *d_memory_ops, void *d_scratch, void *ctx);
+GlError gl_keccak_sponge_table_program(GlGatePrograms *out);
+/* Measurement hook: gl_keccak_sponge_table_trace with an event between its stages. h_ms[4] receives the milliseconds of the
+ * counting pass, the row-to-operation map, the chain kernel and the rows kernel; the host's wait for the count lies between the
+ * first and the second and belongs to none. d_trace and num_ops >= 1 are required. Creates and destroys its events and waits for
+ * ctx->stream before it returns: not for use next to a proof in flight on the same context. */
+GlError gl_debug_keccak_sponge_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, const uint8_t *d_bytes, uint32_t degree_bits,
+                                              uint64_t *d_trace, uint64_t trace_stride, void *d_scratch, float *h_ms, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

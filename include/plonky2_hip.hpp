@@ -492,6 +492,35 @@ inline LogicTableProgram logic_table_program() {
     return out;
 }
 
+// The Keccak sponge table (plonky2_hip.h "The Keccak sponge table"). keccak_sponge_table_trace: d_ops [num_ops][5] records
+// (context, segment, virt, timestamp, len) and the concatenated input bytes -> d_trace [414][trace_stride] with 2^degree_bits
+// rows; returns the rows the operations take, which is all a call with d_trace == nullptr computes. d_scratch:
+// gl_keccak_sponge_table_scratch_bytes(num_ops, degree_bits) bytes in HBM. The call waits once, for the count.
+// keccak_sponge_table_ops: from the finished trace, the records gl_keccak_table_trace, gl_logic_table_trace and
+// gl_memory_table_trace take; any output may be nullptr. keccak_sponge_table_program: the reference's to-do list of constraints
+// written out (constraint_degree 3, no public inputs, no pairs).
+inline uint64_t keccak_sponge_table_trace(const Context &ctx, const uint64_t *d_ops, uint64_t num_ops, const uint8_t *d_bytes, uint32_t degree_bits,
+                                          uint64_t *d_trace, uint64_t trace_stride, void *d_scratch) {
+    uint64_t rows = 0;
+    check(gl_keccak_sponge_table_trace(d_ops, num_ops, d_bytes, degree_bits, d_trace, trace_stride, d_scratch, &rows, ctx.get()));
+    return rows;
+}
+inline void keccak_sponge_table_ops(const Context &ctx, const uint64_t *d_trace, uint64_t trace_stride, uint32_t degree_bits, uint64_t rows,
+                                    uint64_t *d_keccak_inputs, uint64_t *d_logic_ops, uint64_t *d_memory_ops, void *d_scratch) {
+    check(gl_keccak_sponge_table_ops(d_trace, trace_stride, degree_bits, rows, d_keccak_inputs, d_logic_ops, d_memory_ops, d_scratch, ctx.get()));
+}
+using KeccakSpongeTableProgram = KeccakTableProgram;  // instructions, immediates and the number of constraints
+inline KeccakSpongeTableProgram keccak_sponge_table_program() {
+    GlGatePrograms p;
+    check(gl_keccak_sponge_table_program(&p));
+    KeccakSpongeTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 // gl_stark_split_program: the unit programs gl_stark_compile_units cuts desc's program into (device-free). Every unit is a
 // program of its own over desc's immediates; its EMITs are numbers emit_start .. emit_end - 1 of the program's.
 struct StarkProgramUnit {

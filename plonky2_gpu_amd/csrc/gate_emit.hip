@@ -1306,6 +1306,137 @@ Program program(ImmediatePool &pool) {
 
 }  // namespace logic_table
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the Keccak sponge table as ONE STARK program: plonky2_gpu_amd/keccak_sponge_table.py program(), call for call
+// (tests/test_keccak_sponge_table_ref.py holds the two against each other word for word). The reference's eval_packed_generic for
+// this table is a list of TODOs (evm/src/keccak_sponge/keccak_sponge_stark.rs:363-377); this is that list written out, in its
+// order — the reference's to-do list, not a soundness claim: nothing here ties xored_rate_u32s to the block, for example, which
+// is the logic lookup's job. "before_rate_bits" and "block_bits" name columns the layout does not have; nothing is emitted for them.
+namespace keccak_sponge_table {
+
+// columns.rs:15-60
+enum {
+    IS_FULL_INPUT_BLOCK = 0,
+    IS_FINAL_BLOCK = 1,
+    CONTEXT = 2,
+    SEGMENT = 3,
+    VIRT = 4,
+    TIMESTAMP = 5,
+    LEN = 6,
+    ALREADY_ABSORBED_BYTES = 7,
+    IS_FINAL_INPUT_LEN = 8,
+    ORIGINAL_RATE_U32S = 144,  // the 16 of original_capacity_u32s follow its 34
+    UPDATED_STATE_U32S = 364,
+    RATE_BYTES = 136,
+    WIDTH_U32S = 50,
+};
+
+Program program(ImmediatePool &pool) {
+    keccak_table::Asm a(&pool);
+    auto boolean = [&](int column) {
+        a.release();
+        const int flag = a.local(column);
+        const int one = a.imm(1);
+        const int t = a.sub(flag, one);
+        a.emit(a.mul(flag, t));
+    };
+    // each flag is boolean, and so is the implied dummy flag 1 - F - L: F L = 0
+    boolean(IS_FULL_INPUT_BLOCK);
+    boolean(IS_FINAL_BLOCK);
+    {
+        a.release();
+        const int full = a.local(IS_FULL_INPUT_BLOCK);
+        const int fin = a.local(IS_FINAL_BLOCK);
+        a.emit(a.mul(full, fin));
+    }
+    // is_final_input_len contains booleans
+    for (int i = 0; i < RATE_BYTES; i++) boolean(IS_FINAL_INPUT_LEN + i);
+    // their sum equals is_final_block
+    {
+        a.release();
+        for (int i = 0; i < RATE_BYTES; i++) {
+            const int t = a.local(IS_FINAL_INPUT_LEN + i);
+            a.acc(t, 1);
+            a.free1(t);
+        }
+        const int sum = a.accr();
+        const int fin = a.local(IS_FINAL_BLOCK);
+        a.emit(a.sub(sum, fin));
+    }
+    // the columns that are zero where a sponge starts: the original state, then already_absorbed_bytes
+    int fresh[WIDTH_U32S + 1];
+    for (int j = 0; j < WIDTH_U32S; j++) fresh[j] = ORIGINAL_RATE_U32S + j;
+    fresh[WIDTH_U32S] = ALREADY_ABSORBED_BYTES;
+    // the first row starts a sponge
+    for (int column : fresh) {
+        a.release();
+        a.emit_first_row(a.local(column));
+    }
+    // behind a final block the next row starts one
+    for (int column : fresh) {
+        a.release();
+        const int fin = a.local(IS_FINAL_BLOCK);
+        const int nxt = a.next(column);
+        a.emit_transition(a.mul(fin, nxt));
+    }
+    // behind a full-input block the next row's address, time and len match
+    for (int column : {CONTEXT, SEGMENT, VIRT, TIMESTAMP, LEN}) {
+        a.release();
+        const int full = a.local(IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(column);
+        const int local = a.local(column);
+        const int diff = a.sub(nxt, local);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // ... its "before" is our "after"
+    for (int j = 0; j < WIDTH_U32S; j++) {
+        a.release();
+        const int full = a.local(IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(ORIGINAL_RATE_U32S + j);
+        const int updated = a.local(UPDATED_STATE_U32S + j);
+        const int diff = a.sub(nxt, updated);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // ... and its already_absorbed_bytes is ours plus 136
+    {
+        a.release();
+        const int full = a.local(IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(ALREADY_ABSORBED_BYTES);
+        const int local = a.local(ALREADY_ABSORBED_BYTES);
+        const int diff = a.sub(nxt, local);
+        const int rate = a.imm(RATE_BYTES);
+        a.sub(diff, rate, diff);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // a dummy row is followed by a dummy row
+    {
+        a.release();
+        const int dummy = a.imm(1);
+        const int full = a.local(IS_FULL_INPUT_BLOCK);
+        a.sub(dummy, full, dummy);
+        const int fin = a.local(IS_FINAL_BLOCK);
+        a.sub(dummy, fin, dummy);
+        const int next_full = a.next(IS_FULL_INPUT_BLOCK);
+        const int next_fin = a.next(IS_FINAL_BLOCK);
+        const int next_used = a.add(next_full, next_fin);
+        a.emit_transition(a.mul(dummy, next_used));
+    }
+    // is_final_input_len[i] implies len - already_absorbed_bytes == i
+    for (int i = 0; i < RATE_BYTES; i++) {
+        a.release();
+        const int flag = a.local(IS_FINAL_INPUT_LEN + i);
+        const int len = a.local(LEN);
+        const int absorbed = a.local(ALREADY_ABSORBED_BYTES);
+        const int diff = a.sub(len, absorbed);
+        const int index = a.imm(i);
+        a.sub(diff, index, diff);
+        a.emit(a.mul(flag, diff));
+    }
+    return a.instrs;
+}
+
+}  // namespace keccak_sponge_table
+
 // a table's STARK program as a GlGatePrograms without gate descriptors; num_gate_constraints counts its EMITs of every kind
 GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePool &), GlGatePrograms *out) {
     if (!out) return emit_error(name + ": null pointer");
@@ -1343,6 +1474,10 @@ extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) { return emit_ta
 extern "C" GlError gl_memory_table_program(GlGatePrograms *out) { return emit_table_program("gl_memory_table_program", memory_table::program, out); }
 
 extern "C" GlError gl_logic_table_program(GlGatePrograms *out) { return emit_table_program("gl_logic_table_program", logic_table::program, out); }
+
+extern "C" GlError gl_keccak_sponge_table_program(GlGatePrograms *out) {
+    return emit_table_program("gl_keccak_sponge_table_program", keccak_sponge_table::program, out);
+}
 
 extern "C" GlError gl_gate_programs_emit(const GlGateSpec *gates, uint32_t num_gates, const uint32_t *group_bounds, uint32_t num_selectors,
                                          GlGatePrograms *out) {
