@@ -14,190 +14,14 @@
 //                                                  reducing_extension,exponentiation,poseidon_mds,low_degree_interpolation,high_degree_interpolation}.rs
 // The output is identical, instruction for instruction and immediate for immediate, to gate_program.py's
 // (tests/test_gate_emit.py), which the oracle's gate restatements check (tests/test_gate_programs_cpu.py).
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "../../include/plonky2_hip.h"
-#include "gl_field.h"
-#include "program_isa.h"
+// The assembler (GateAsm, ImmediatePool) is program_asm.h's; the tables' STARK programs are built on it in their own <table>.hip.
+#include "program_asm.h"
 #define POSEIDON_CONST static const
 #include "poseidon_constants.h"
 
 namespace {
 
-using namespace plonky2_hip::isa;  // the opcodes, MAX_REGS, AccBound
-
-typedef unsigned __int128 u128;
-constexpr uint64_t P = glh::P;
-const u128 ACC_LIMIT = AccBound::LIMIT;  // each half of an accumulator stays below this (gl::fold96's precondition)
-
-// Field constants referenced by LOAD_IMM / ACC, shared by all gates of a circuit (deduplicated)
-struct ImmediatePool {
-    std::vector<uint64_t> values;
-    std::map<uint64_t, uint32_t> index_of;
-    uint32_t index(u128 value) {
-        const uint64_t v = (uint64_t)(value % P);
-        auto it = index_of.find(v);
-        if (it != index_of.end()) return it->second;
-        if (values.size() >= 65536) throw std::runtime_error("more than 65536 distinct immediates");
-        const uint32_t i = (uint32_t)values.size();
-        index_of[v] = i;
-        values.push_back(v);
-        return i;
-    }
-};
-
-u128 ipow(u128 base, unsigned e) {
-    u128 r = 1;
-    for (unsigned i = 0; i < e; i++) r *= base;
-    return r;
-}
-
-// Emits one gate's register program. Registers come from a free list (lowest first; freed registers are reused last in,
-// first out); release() returns all of them (between independent constraints).
-struct GateAsm {
-    std::vector<GlGateInstr> instrs;
-    ImmediatePool *pool;
-    std::vector<int> free_list;
-    AccBound acc_bound[MAX_ACCS];
-
-    explicit GateAsm(ImmediatePool *p = nullptr) : pool(p) { release(); }
-    void release() {
-        free_list.clear();
-        for (int r = (int)MAX_REGS - 1; r >= 0; r--) free_list.push_back(r);
-    }
-    int reg() {
-        if (free_list.empty()) throw std::runtime_error("gate program needs more than 64 live registers");
-        const int r = free_list.back();
-        free_list.pop_back();
-        return r;
-    }
-    void free1(int r) {
-        if (std::find(free_list.begin(), free_list.end(), r) != free_list.end()) throw std::runtime_error("register freed twice");
-        free_list.push_back(r);
-    }
-    void free(std::initializer_list<int> regs) {
-        for (int r : regs) free1(r);
-    }
-    // operands are 16-bit fields of the instruction word: an index that does not fit is an error, never a wrapped "valid" program
-    static uint16_t field(long v) {
-        if (v < 0 || v > 0xFFFF) throw std::runtime_error("gate program operand (wire, constant, immediate or register index) does not fit 16 bits");
-        return (uint16_t)v;
-    }
-    int op(uint16_t code, int a, int b = 0, int dst = -1) {
-        const int r = dst < 0 ? reg() : dst;
-        instrs.push_back(GlGateInstr{code, field(r), field(a), field(b)});
-        return r;
-    }
-    int wire(int i) { return op(LOAD_WIRE, i); }
-    int constant(int i) { return op(LOAD_CONST, i); }
-    int pi(int i) { return op(LOAD_PI, i); }
-    ImmediatePool &need_pool() {
-        if (!pool) throw std::runtime_error("this gate needs an ImmediatePool");
-        return *pool;
-    }
-    int imm(u128 value) { return op(LOAD_IMM, (int)need_pool().index(value)); }
-    int add(int a, int b, int dst = -1) { return op(ADD, a, b, dst); }
-    int sub(int a, int b, int dst = -1) { return op(SUB, a, b, dst); }
-    int mul(int a, int b, int dst = -1) { return op(MUL, a, b, dst); }
-    int mulk(int a, int shift, int dst = -1) { return op(MULK, a, shift, dst); }
-    void emit(int a) { instrs.push_back(GlGateInstr{EMIT, 0, field(a), 0}); }
-
-    // may r * weight still be added to accumulator q without either half being able to reach 2^63?
-    bool acc_fits(u128 weight, int q = 0) const { return acc_bound[q].fits(weight); }
-    // acc[q] += r[a] * weight, without a modular step (ACC): weight < 2^32, bound checked here
-    void acc(int a, u128 weight = 1, int q = 0) {
-        ImmediatePool &pl = need_pool();
-        if (!acc_bound[q].add(weight)) throw std::runtime_error("accumulator could overflow: reduce (accr) earlier");
-        instrs.push_back(GlGateInstr{ACC, field(q), field(a), field((long)pl.index(weight))});
-    }
-    // register <- acc[q] mod p; acc[q] <- 0 (ACCR)
-    int accr(int q = 0, int dst = -1) {
-        acc_bound[q].reset();
-        return op(ACCR, q, 0, dst);
-    }
-    // sum_i r[reg_i] * weight_i through accumulator q; reduces in between only if the static bound demands it
-    int weighted_sum(const std::vector<std::pair<int, uint64_t>> &terms, int q = 0, int dst = -1) {
-        bool started = false;
-        for (auto &t : terms) {
-            if (started && !acc_fits(t.second, q)) {
-                const int part = accr(q);
-                acc(part, 1, q);
-                free1(part);
-            }
-            acc(t.first, t.second, q);
-            started = true;
-        }
-        if (!started) return op(LOAD_IMM, (int)need_pool().index(0), 0, dst);
-        return accr(q, dst);
-    }
-    // sum terms[i] * base^i (plonk_common.rs:116-128) for an integer base; returns a fresh register. `terms` are registers, or
-    // with wires = true wire indices that are loaded for the purpose. Blocks of consecutive terms whose weights stay below 2^32
-    // and provably fit one accumulation, joined by Horner steps with base^(block length).
-    int reduce_with_powers(const std::vector<int> &terms, uint64_t base, bool wires = false, int q = 0) {
-        if (terms.empty()) return imm(0);
-        std::vector<std::pair<int, unsigned>> blocks;
-        size_t i = 0;
-        while (i < terms.size()) {
-            unsigned j = 0;
-            u128 bound = 0;
-            while (i + j < terms.size() && ipow(base, j) < ((u128)1 << 32) && bound + ipow(base, j) * 0xFFFFFFFFull < ACC_LIMIT) {
-                bound += ipow(base, j) * 0xFFFFFFFFull;
-                j++;
-            }
-            for (unsigned k = 0; k < j; k++) {
-                const int t = wires ? wire(terms[i + k]) : terms[i + k];
-                acc(t, ipow(base, k), q);
-                if (wires) free1(t);
-            }
-            blocks.push_back({accr(q), j});
-            i += j;
-        }
-        const int accu = blocks.back().first;
-        for (size_t b = blocks.size() - 1; b-- > 0;) {
-            const u128 step = ipow(base, blocks[b].second);
-            unsigned bits = 0;
-            while (((u128)1 << bits) < step) bits++;
-            if ((step & (step - 1)) == 0 && bits < 64) {
-                mulk(accu, (int)bits, accu);
-            } else {
-                const int m = imm(step % P);
-                mul(accu, m, accu);
-                free1(m);
-            }
-            add(accu, blocks[b].first, accu);
-            free1(blocks[b].first);
-        }
-        return accu;
-    }
-    // prod_{k < len(small)} (x - k); small[k] = register holding the constant k. For four factors y (y + 2) with y = x (x - 3).
-    int range_product(int x, const std::vector<int> &small) {
-        if (small.size() == 4) {
-            const int t = sub(x, small[3]);
-            const int y = mul(x, t);
-            add(y, small[2], t);
-            mul(y, t, y);
-            free1(t);
-            return y;
-        }
-        const int a = sub(x, small[0]);
-        for (size_t k = 1; k < small.size(); k++) {
-            const int t = sub(x, small[k]);
-            mul(a, t, a);
-            free1(t);
-        }
-        return a;
-    }
-};
-
-typedef std::vector<GlGateInstr> Program;
+using namespace plonky2_hip::program_asm;  // GateAsm, ImmediatePool, Program, ipow; the opcodes of program_isa.h
 
 // ArithmeticGate { num_ops } (plonky2/src/gates/arithmetic_base.rs:199-216)
 Program arithmetic_gate(unsigned num_ops) {
@@ -916,568 +740,7 @@ Program build_gate(const GlGateSpec &s, ImmediatePool &pool) {
     }
 }
 
-GlError emit_error(const std::string &msg) {
-    GlError e;
-    e.code = -1;
-    e.message = strdup(msg.c_str());
-    return e;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The constraints of the reference's Keccak-f table (evm/src/keccak/keccak_stark.rs:230-375 with round_flags.rs:12-27 and
-// logic.rs) as ONE STARK program: plonky2_gpu_amd/keccak_table.py program(), call for call (tests/test_keccak_table_ref.py holds
-// the two against each other word for word).
-namespace keccak_table {
-
-constexpr int NUM_ROUNDS = 24;
-const uint64_t RC[NUM_ROUNDS] = {
-    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull, 0x000000000000808Bull, 0x0000000080000001ull,
-    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008Aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000Aull,
-    0x000000008000808Bull, 0x800000000000008Bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
-    0x000000000000800Aull, 0x800000008000000Aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
-const int R[5][5] = {{0, 36, 3, 41, 18}, {1, 44, 10, 45, 2}, {62, 6, 43, 15, 61}, {28, 55, 25, 21, 56}, {27, 20, 39, 8, 14}};
-
-// columns.rs
-int reg_step(int i) { return i; }
-int reg_a(int x, int y) { return 24 + (x * 5 + y) * 2; }
-int reg_c(int x, int z) { return 74 + x * 64 + z; }
-int reg_c_prime(int x, int z) { return 394 + x * 64 + z; }
-int reg_a_prime(int x, int y, int z) { return 714 + x * 64 * 5 + y * 64 + z; }
-int reg_b(int x, int y, int z) {
-    const int a = (x + 3 * y) % 5;
-    return reg_a_prime(a, x, (z + 64 - R[a][x]) % 64);
-}
-int reg_a_prime_prime(int x, int y) { return 2314 + x * 2 * 5 + y * 2; }
-int reg_a_prime_prime_0_0_bit(int i) { return 2364 + i; }
-int reg_a_prime_prime_prime(int x, int y) { return x == 0 && y == 0 ? 2428 : reg_a_prime_prime(x, y); }
-
-struct Asm : GateAsm {
-    explicit Asm(ImmediatePool *p) : GateAsm(p) {}
-    int local(int i) { return op(LOAD_WIRE, i); }
-    int next(int i) { return op(LOAD_NEXT, i); }
-    void emit_transition(int a) { instrs.push_back(GlGateInstr{EMIT_TRANSITION, 0, field(a), 0}); }
-    void emit_first_row(int a) { instrs.push_back(GlGateInstr{EMIT_FIRST_ROW, 0, field(a), 0}); }
-    // xor_gen(x, y) = x + y - 2 x y in a fresh register; x and y stay
-    int xor2(int x, int y) {
-        const int s = add(x, y);
-        const int m = mul(x, y);
-        mulk(m, 1, m);
-        sub(s, m, s);
-        free1(m);
-        return s;
-    }
-    // xor3_gen(x, y, z) = xor_gen(x, xor_gen(y, z))
-    int xor3(int x, int y, int z) {
-        const int t = xor2(y, z);
-        const int u = xor2(x, t);
-        free1(t);
-        return u;
-    }
-    // sum_{k < 32} 2^k bit(z0 + k) in two blocks of 16 weights joined by a shift; bit(z) returns a register that is freed here
-    template <class Bit>
-    int limb(Bit bit, int z0) {
-        int halves[2];
-        for (int h = 0; h < 2; h++) {
-            for (int k = 0; k < 16; k++) {
-                const int t = bit(z0 + 16 * h + k);
-                acc(t, (u128)1 << k);
-                free1(t);
-            }
-            halves[h] = accr();
-        }
-        const int lo = halves[0], hi = halves[1];
-        mulk(hi, 16, hi);
-        add(hi, lo, hi);
-        free1(lo);
-        return hi;
-    }
-};
-
-Program program(ImmediatePool &pool) {
-    Asm a(&pool);
-    // eval_round_flags
-    {
-        const int s0 = a.local(reg_step(0));
-        const int one = a.imm(1);
-        a.emit_first_row(a.sub(s0, one));
-    }
-    for (int i = 1; i < NUM_ROUNDS; i++) {
-        a.release();
-        a.emit_first_row(a.local(reg_step(i)));
-    }
-    for (int i = 0; i < NUM_ROUNDS; i++) {
-        a.release();
-        const int nx = a.next(reg_step((i + 1) % NUM_ROUNDS));
-        const int lc = a.local(reg_step(i));
-        a.emit_transition(a.sub(nx, lc));
-    }
-    // C'[x, z] = xor(C[x, z], C[x - 1, z], C[x + 1, z - 1])
-    for (int x = 0; x < 5; x++)
-        for (int z = 0; z < 64; z++) {
-            a.release();
-            const int c0 = a.local(reg_c(x, z));
-            const int c1 = a.local(reg_c((x + 4) % 5, z));
-            const int c2 = a.local(reg_c((x + 1) % 5, (z + 63) % 64));
-            const int x3 = a.xor3(c0, c1, c2);
-            const int cp = a.local(reg_c_prime(x, z));
-            a.emit(a.sub(cp, x3));
-        }
-    // A[x, y, z] = xor(A'[x, y, z], C[x, z], C'[x, z]), recomposed into the two input limbs
-    for (int x = 0; x < 5; x++)
-        for (int y = 0; y < 5; y++) {
-            auto bit = [&](int z) {
-                const int ap = a.local(reg_a_prime(x, y, z));
-                const int c = a.local(reg_c(x, z));
-                const int cp = a.local(reg_c_prime(x, z));
-                const int t = a.xor3(ap, c, cp);
-                a.free({ap, c, cp});
-                return t;
-            };
-            for (int l = 0; l < 2; l++) {
-                a.release();
-                const int computed = a.limb(bit, 32 * l);
-                const int al = a.local(reg_a(x, y) + l);
-                a.emit(a.sub(computed, al));
-            }
-        }
-    // diff (diff - 2) (diff - 4) = 0 with diff = sum_i A'[x, i, z] - C'[x, z]
-    for (int x = 0; x < 5; x++)
-        for (int z = 0; z < 64; z++) {
-            a.release();
-            const int s = a.local(reg_a_prime(x, 0, z));
-            for (int i = 1; i < 5; i++) {
-                const int t = a.local(reg_a_prime(x, i, z));
-                a.add(s, t, s);
-                a.free1(t);
-            }
-            const int cp = a.local(reg_c_prime(x, z));
-            const int diff = a.sub(s, cp);
-            const int two = a.imm(2);
-            const int d2 = a.sub(diff, two);
-            const int four = a.imm(4);
-            const int d4 = a.sub(diff, four);
-            const int m = a.mul(diff, d2);
-            a.emit(a.mul(m, d4));
-        }
-    // A''[x, y] = xor(B[x, y], andn(B[x + 1, y], B[x + 2, y]))
-    for (int x = 0; x < 5; x++)
-        for (int y = 0; y < 5; y++)
-            for (int l = 0; l < 2; l++) {
-                a.release();
-                const int one = a.imm(1);
-                auto bit = [&](int z) {
-                    const int b0 = a.local(reg_b(x, y, z));
-                    const int b1 = a.local(reg_b((x + 1) % 5, y, z));
-                    const int b2 = a.local(reg_b((x + 2) % 5, y, z));
-                    const int n = a.sub(one, b1);
-                    a.mul(n, b2, n);  // andn_gen(x, y) = (1 - x) y
-                    const int t = a.xor2(b0, n);
-                    a.free({b0, b1, b2, n});
-                    return t;
-                };
-                const int computed = a.limb(bit, 32 * l);
-                const int app = a.local(reg_a_prime_prime(x, y) + l);
-                a.emit(a.sub(computed, app));
-            }
-    // A'''[0, 0] = A''[0, 0] xor RC: the bits of A''[0, 0] recompose into its limbs ...
-    for (int l = 0; l < 2; l++) {
-        a.release();
-        const int computed = a.limb([&](int z) { return a.local(reg_a_prime_prime_0_0_bit(z)); }, 32 * l);
-        const int app = a.local(reg_a_prime_prime(0, 0) + l);
-        a.emit(a.sub(computed, app));
-    }
-    // ... and xored with the round's constant into the limbs of A'''[0, 0]
-    auto xored_bit = [&](int i) {
-        const int b = a.local(reg_a_prime_prime_0_0_bit(i));
-        bool any = false;
-        for (int r = 0; r < NUM_ROUNDS; r++)
-            if ((RC[r] >> i) & 1) {
-                const int f = a.local(reg_step(r));
-                a.acc(f, 1, 1);
-                a.free1(f);
-                any = true;
-            }
-        if (!any) return b;
-        const int rc = a.accr(1);
-        const int t = a.xor2(b, rc);
-        a.free({b, rc});
-        return t;
-    };
-    for (int l = 0; l < 2; l++) {
-        a.release();
-        const int computed = a.limb(xored_bit, 32 * l);
-        const int appp = a.local(reg_a_prime_prime_prime(0, 0) + l);
-        a.emit(a.sub(computed, appp));
-    }
-    // this round's output is the next round's input, except behind the last round
-    for (int x = 0; x < 5; x++)
-        for (int y = 0; y < 5; y++)
-            for (int l = 0; l < 2; l++) {
-                a.release();
-                const int one = a.imm(1);
-                const int last = a.local(reg_step(NUM_ROUNDS - 1));
-                const int not_last = a.sub(one, last);
-                const int out = a.local(reg_a_prime_prime_prime(x, y) + l);
-                const int in = a.next(reg_a(x, y) + l);
-                const int diff = a.sub(out, in);
-                a.emit_transition(a.mul(not_last, diff));
-            }
-    return a.instrs;
-}
-
-}  // namespace keccak_table
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The constraints of the reference's memory table (evm/src/memory/memory_stark.rs:242-319 with lookup.rs:19-33) as ONE STARK
-// program: plonky2_gpu_amd/memory_table.py program(), call for call (tests/test_memory_table_ref.py holds the two against each
-// other word for word).
-namespace memory_table {
-
-// columns.rs
-enum {
-    FILTER = 0,
-    TIMESTAMP = 1,
-    IS_READ = 2,
-    ADDR_CONTEXT = 3,
-    ADDR_SEGMENT = 4,
-    ADDR_VIRTUAL = 5,
-    VALUE_START = 6,
-    CONTEXT_FIRST_CHANGE = 14,
-    SEGMENT_FIRST_CHANGE = 15,
-    VIRTUAL_FIRST_CHANGE = 16,
-    RANGE_CHECK = 22,
-    RANGE_CHECK_PERMUTED = 24,
-    COUNTER_PERMUTED = 25,
-};
-
-struct Asm : keccak_table::Asm {
-    explicit Asm(ImmediatePool *p) : keccak_table::Asm(p) {}
-    void emit_last_row(int a) { instrs.push_back(GlGateInstr{EMIT_LAST_ROW, 0, field(a), 0}); }
-    // eval_lookups (evm/src/lookup.rs:19-33), as StarkAsm.eval_lookups
-    void eval_lookups(int col_permuted_input, int col_permuted_table) {
-        const int local_perm_input = local(col_permuted_input);
-        const int next_perm_table = next(col_permuted_table);
-        const int next_perm_input = next(col_permuted_input);
-        const int diff_input_prev = sub(next_perm_input, local_perm_input);
-        const int diff_input_table = sub(next_perm_input, next_perm_table);
-        emit(mul(diff_input_prev, diff_input_table));
-        emit_last_row(diff_input_table);
-    }
-};
-
-Program program(ImmediatePool &pool) {
-    Asm a(&pool);
-    const int one = a.imm(1);
-    // the filter is 0 or 1
-    const int filter = a.local(FILTER);
-    {
-        const int t = a.sub(filter, one);
-        a.mul(filter, t, t);
-        a.emit(t);
-        a.free1(t);
-    }
-    // a dummy row (filter off) is a read
-    {
-        const int is_dummy = a.sub(one, filter);
-        const int is_read = a.local(IS_READ);
-        const int is_write = a.sub(one, is_read);
-        const int t = a.mul(is_dummy, is_write);
-        a.emit(t);
-        a.free({t, is_dummy, is_write, is_read, filter});
-    }
-    // first set of ordering constraints: the first_change flags and address_unchanged are boolean
-    const int context_first_change = a.local(CONTEXT_FIRST_CHANGE);
-    const int segment_first_change = a.local(SEGMENT_FIRST_CHANGE);
-    const int virtual_first_change = a.local(VIRTUAL_FIRST_CHANGE);
-    const int address_unchanged = a.sub(one, context_first_change);
-    a.sub(address_unchanged, segment_first_change, address_unchanged);
-    a.sub(address_unchanged, virtual_first_change, address_unchanged);
-    for (int flag : {context_first_change, segment_first_change, virtual_first_change, address_unchanged}) {
-        const int t = a.sub(one, flag);
-        a.mul(flag, t, t);
-        a.emit(t);
-        a.free1(t);
-    }
-    // second set: no change before the column of the flag that is set
-    int diffs[4];
-    const int diff_columns[4] = {ADDR_CONTEXT, ADDR_SEGMENT, ADDR_VIRTUAL, TIMESTAMP};
-    for (int k = 0; k < 4; k++) {
-        const int nxt = a.next(diff_columns[k]);
-        const int local = a.local(diff_columns[k]);
-        a.sub(nxt, local, nxt);
-        a.free1(local);
-        diffs[k] = nxt;
-    }
-    const int d_context = diffs[0], d_segment = diffs[1], d_virtual = diffs[2], d_timestamp = diffs[3];
-    const int transitions[6][2] = {{segment_first_change, d_context}, {virtual_first_change, d_context}, {virtual_first_change, d_segment},
-                                   {address_unchanged, d_context},    {address_unchanged, d_segment},    {address_unchanged, d_virtual}};
-    for (const auto &fd : transitions) {
-        const int t = a.mul(fd[0], fd[1]);
-        a.emit_transition(t);
-        a.free1(t);
-    }
-    // third set: the range check is the difference of the column that should be increasing
-    {
-        const int computed = a.sub(d_context, one);
-        a.mul(context_first_change, computed, computed);
-        const int terms[2][2] = {{segment_first_change, d_segment}, {virtual_first_change, d_virtual}};
-        for (const auto &fd : terms) {
-            const int t = a.sub(fd[1], one);
-            a.mul(fd[0], t, t);
-            a.add(computed, t, computed);
-            a.free1(t);
-        }
-        const int t = a.mul(address_unchanged, d_timestamp);
-        a.add(computed, t, computed);
-        a.free1(t);
-        const int range_check = a.local(RANGE_CHECK);
-        a.sub(range_check, computed, computed);
-        a.emit_transition(computed);
-        a.free({computed, range_check});
-    }
-    // the purportedly ordered log: a read of an unchanged address sees the value of the row before
-    const int gate = a.next(IS_READ);
-    a.mul(gate, address_unchanged, gate);
-    for (int i = 0; i < 8; i++) {
-        const int nxt = a.next(VALUE_START + i);
-        const int local = a.local(VALUE_START + i);
-        a.sub(nxt, local, nxt);
-        a.mul(gate, nxt, nxt);
-        a.emit(nxt);
-        a.free({nxt, local});
-    }
-    a.release();
-    a.eval_lookups(RANGE_CHECK_PERMUTED, COUNTER_PERMUTED);
-    return a.instrs;
-}
-
-}  // namespace memory_table
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The constraints of the reference's logic table (evm/src/logic.rs:182-231) as ONE STARK program:
-// plonky2_gpu_amd/logic_table.py program(), call for call (tests/test_logic_table_ref.py holds the two against each other word
-// for word).
-namespace logic_table {
-
-// logic.rs:28-52
-enum { IS_AND = 0, IS_OR = 1, IS_XOR = 2, INPUT0 = 3, INPUT1 = 259, RESULT = 515, VAL_BITS = 256, PACKED_LEN = 8 };
-
-Program program(ImmediatePool &pool) {
-    keccak_table::Asm a(&pool);
-    // all bits are indeed bits
-    for (int start : {INPUT0, INPUT1})
-        for (int i = 0; i < VAL_BITS; i++) {
-            a.release();
-            const int bit = a.local(start + i);
-            const int one = a.imm(1);
-            const int t = a.sub(bit, one);
-            a.emit(a.mul(bit, t));
-        }
-    // RESULT[i] = sum_coeff (x + y) + and_coeff (x AND y) on the limb's 32 bits
-    for (int i = 0; i < PACKED_LEN; i++) {
-        a.release();
-        const int x = a.limb([&](int z) { return a.local(INPUT0 + z); }, 32 * i);
-        const int y = a.limb([&](int z) { return a.local(INPUT1 + z); }, 32 * i);
-        const int x_land_y = a.limb(
-            [&](int z) {
-                const int x_bit = a.local(INPUT0 + z);
-                const int y_bit = a.local(INPUT1 + z);
-                a.mul(x_bit, y_bit, x_bit);
-                a.free1(y_bit);
-                return x_bit;
-            },
-            32 * i);
-        const int is_and = a.local(IS_AND);
-        const int is_or = a.local(IS_OR);
-        const int is_xor = a.local(IS_XOR);
-        const int sum_coeff = a.add(is_or, is_xor);
-        const int and_coeff = a.sub(is_and, is_or);
-        a.mulk(is_xor, 1, is_xor);
-        a.sub(and_coeff, is_xor, and_coeff);
-        a.add(x, y, x);
-        a.mul(sum_coeff, x, x);
-        a.mul(and_coeff, x_land_y, x_land_y);
-        a.add(x, x_land_y, x);
-        const int result = a.local(RESULT + i);
-        a.emit(a.sub(result, x));
-    }
-    return a.instrs;
-}
-
-}  // namespace logic_table
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The constraints of the Keccak sponge table as ONE STARK program: plonky2_gpu_amd/keccak_sponge_table.py program(), call for call
-// (tests/test_keccak_sponge_table_ref.py holds the two against each other word for word). The reference's eval_packed_generic for
-// this table is a list of TODOs (evm/src/keccak_sponge/keccak_sponge_stark.rs:363-377); this is that list written out, in its
-// order — the reference's to-do list, not a soundness claim: nothing here ties xored_rate_u32s to the block, for example, which
-// is the logic lookup's job. "before_rate_bits" and "block_bits" name columns the layout does not have; nothing is emitted for them.
-namespace keccak_sponge_table {
-
-// columns.rs:15-60
-enum {
-    IS_FULL_INPUT_BLOCK = 0,
-    IS_FINAL_BLOCK = 1,
-    CONTEXT = 2,
-    SEGMENT = 3,
-    VIRT = 4,
-    TIMESTAMP = 5,
-    LEN = 6,
-    ALREADY_ABSORBED_BYTES = 7,
-    IS_FINAL_INPUT_LEN = 8,
-    ORIGINAL_RATE_U32S = 144,  // the 16 of original_capacity_u32s follow its 34
-    UPDATED_STATE_U32S = 364,
-    RATE_BYTES = 136,
-    WIDTH_U32S = 50,
-};
-
-Program program(ImmediatePool &pool) {
-    keccak_table::Asm a(&pool);
-    auto boolean = [&](int column) {
-        a.release();
-        const int flag = a.local(column);
-        const int one = a.imm(1);
-        const int t = a.sub(flag, one);
-        a.emit(a.mul(flag, t));
-    };
-    // each flag is boolean, and so is the implied dummy flag 1 - F - L: F L = 0
-    boolean(IS_FULL_INPUT_BLOCK);
-    boolean(IS_FINAL_BLOCK);
-    {
-        a.release();
-        const int full = a.local(IS_FULL_INPUT_BLOCK);
-        const int fin = a.local(IS_FINAL_BLOCK);
-        a.emit(a.mul(full, fin));
-    }
-    // is_final_input_len contains booleans
-    for (int i = 0; i < RATE_BYTES; i++) boolean(IS_FINAL_INPUT_LEN + i);
-    // their sum equals is_final_block
-    {
-        a.release();
-        for (int i = 0; i < RATE_BYTES; i++) {
-            const int t = a.local(IS_FINAL_INPUT_LEN + i);
-            a.acc(t, 1);
-            a.free1(t);
-        }
-        const int sum = a.accr();
-        const int fin = a.local(IS_FINAL_BLOCK);
-        a.emit(a.sub(sum, fin));
-    }
-    // the columns that are zero where a sponge starts: the original state, then already_absorbed_bytes
-    int fresh[WIDTH_U32S + 1];
-    for (int j = 0; j < WIDTH_U32S; j++) fresh[j] = ORIGINAL_RATE_U32S + j;
-    fresh[WIDTH_U32S] = ALREADY_ABSORBED_BYTES;
-    // the first row starts a sponge
-    for (int column : fresh) {
-        a.release();
-        a.emit_first_row(a.local(column));
-    }
-    // behind a final block the next row starts one
-    for (int column : fresh) {
-        a.release();
-        const int fin = a.local(IS_FINAL_BLOCK);
-        const int nxt = a.next(column);
-        a.emit_transition(a.mul(fin, nxt));
-    }
-    // behind a full-input block the next row's address, time and len match
-    for (int column : {CONTEXT, SEGMENT, VIRT, TIMESTAMP, LEN}) {
-        a.release();
-        const int full = a.local(IS_FULL_INPUT_BLOCK);
-        const int nxt = a.next(column);
-        const int local = a.local(column);
-        const int diff = a.sub(nxt, local);
-        a.emit_transition(a.mul(full, diff));
-    }
-    // ... its "before" is our "after"
-    for (int j = 0; j < WIDTH_U32S; j++) {
-        a.release();
-        const int full = a.local(IS_FULL_INPUT_BLOCK);
-        const int nxt = a.next(ORIGINAL_RATE_U32S + j);
-        const int updated = a.local(UPDATED_STATE_U32S + j);
-        const int diff = a.sub(nxt, updated);
-        a.emit_transition(a.mul(full, diff));
-    }
-    // ... and its already_absorbed_bytes is ours plus 136
-    {
-        a.release();
-        const int full = a.local(IS_FULL_INPUT_BLOCK);
-        const int nxt = a.next(ALREADY_ABSORBED_BYTES);
-        const int local = a.local(ALREADY_ABSORBED_BYTES);
-        const int diff = a.sub(nxt, local);
-        const int rate = a.imm(RATE_BYTES);
-        a.sub(diff, rate, diff);
-        a.emit_transition(a.mul(full, diff));
-    }
-    // a dummy row is followed by a dummy row
-    {
-        a.release();
-        const int dummy = a.imm(1);
-        const int full = a.local(IS_FULL_INPUT_BLOCK);
-        a.sub(dummy, full, dummy);
-        const int fin = a.local(IS_FINAL_BLOCK);
-        a.sub(dummy, fin, dummy);
-        const int next_full = a.next(IS_FULL_INPUT_BLOCK);
-        const int next_fin = a.next(IS_FINAL_BLOCK);
-        const int next_used = a.add(next_full, next_fin);
-        a.emit_transition(a.mul(dummy, next_used));
-    }
-    // is_final_input_len[i] implies len - already_absorbed_bytes == i
-    for (int i = 0; i < RATE_BYTES; i++) {
-        a.release();
-        const int flag = a.local(IS_FINAL_INPUT_LEN + i);
-        const int len = a.local(LEN);
-        const int absorbed = a.local(ALREADY_ABSORBED_BYTES);
-        const int diff = a.sub(len, absorbed);
-        const int index = a.imm(i);
-        a.sub(diff, index, diff);
-        a.emit(a.mul(flag, diff));
-    }
-    return a.instrs;
-}
-
-}  // namespace keccak_sponge_table
-
-// a table's STARK program as a GlGatePrograms without gate descriptors; num_gate_constraints counts its EMITs of every kind
-GlError emit_table_program(const std::string &name, Program (*build)(ImmediatePool &), GlGatePrograms *out) {
-    if (!out) return emit_error(name + ": null pointer");
-    memset(out, 0, sizeof *out);
-    try {
-        ImmediatePool pool;
-        const Program prog = build(pool);
-        uint32_t emits = 0;
-        for (const GlGateInstr &in : prog) emits += is_emit(in.op);
-        out->num_instrs = (uint32_t)prog.size();
-        out->num_immediates = (uint32_t)pool.values.size();
-        out->num_gate_constraints = emits;
-        out->instrs = (GlGateInstr *)malloc(prog.size() * sizeof(GlGateInstr));
-        out->immediates = (uint64_t *)malloc(pool.values.size() * sizeof(uint64_t));
-        if (!out->instrs || !out->immediates) {
-            gl_gate_programs_free(out);
-            return emit_error(name + ": out of memory");
-        }
-        memcpy(out->instrs, prog.data(), prog.size() * sizeof(GlGateInstr));
-        memcpy(out->immediates, pool.values.data(), pool.values.size() * sizeof(uint64_t));
-    } catch (const std::exception &ex) {
-        gl_gate_programs_free(out);
-        return emit_error(name + ": " + ex.what());
-    }
-    GlError ok;
-    ok.code = 0;
-    ok.message = nullptr;
-    return ok;
-}
-
 }  // namespace
-
-extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) { return emit_table_program("gl_keccak_table_program", keccak_table::program, out); }
-
-extern "C" GlError gl_memory_table_program(GlGatePrograms *out) { return emit_table_program("gl_memory_table_program", memory_table::program, out); }
-
-extern "C" GlError gl_logic_table_program(GlGatePrograms *out) { return emit_table_program("gl_logic_table_program", logic_table::program, out); }
-
-extern "C" GlError gl_keccak_sponge_table_program(GlGatePrograms *out) {
-    return emit_table_program("gl_keccak_sponge_table_program", keccak_sponge_table::program, out);
-}
 
 extern "C" GlError gl_gate_programs_emit(const GlGateSpec *gates, uint32_t num_gates, const uint32_t *group_bounds, uint32_t num_selectors,
                                          GlGatePrograms *out) {

@@ -26,6 +26,8 @@
 #include "logic_table.h"
 #include "lookup.h"
 #include "memory_table.h"
+#include "program_asm.h"
+#include "table_args.h"
 
 namespace plonky2_hip {
 
@@ -279,12 +281,6 @@ hipError_t enqueue_count(const uint64_t *d_ops, uint64_t num_ops, const KeccakSp
     return hipGetLastError();
 }
 
-hipError_t read_header(const KeccakSpongeTableScratch &s, KeccakSpongeTableHeader *h, hipStream_t stream) {
-    hipError_t e = hipMemcpyAsync(h, s.header, sizeof(KeccakSpongeTableHeader), hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
-}
-
 hipError_t enqueue_map(uint64_t num_ops, uint64_t rows, const KeccakSpongeTableScratch &s, hipStream_t stream) {
     if (!rows) return hipSuccess;
     ks_map<<<dim3(blocks_for(rows)), dim3(T), 0, stream>>>(s.op_rows, (uint32_t)num_ops, rows, reinterpret_cast<uint32_t *>(s.row_words));
@@ -339,7 +335,7 @@ hipError_t keccak_sponge_table_count(const uint64_t *d_ops, uint64_t num_ops, co
     if (!d_ops || !h || num_ops == 0 || num_ops > KECCAK_SPONGE_TABLE_MAX_OPS) return hipErrorInvalidValue;
     hipError_t e = enqueue_count(d_ops, num_ops, s, stream);
     if (e != hipSuccess) return e;
-    return read_header(s, h, stream);
+    return read_status(h, s.header, sizeof(KeccakSpongeTableHeader), stream);
 }
 
 hipError_t keccak_sponge_table_fill(const uint64_t *d_ops, uint64_t num_ops, const uint8_t *d_bytes, uint64_t rows, uint32_t log_n, uint64_t *d_trace,
@@ -356,30 +352,25 @@ hipError_t keccak_sponge_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops,
                                         uint64_t trace_stride, const KeccakSpongeTableScratch &s, KeccakSpongeTableHeader *h, float *ms,
                                         hipStream_t stream) {
     if (!d_ops || !h || !ms || num_ops == 0 || num_ops > KECCAK_SPONGE_TABLE_MAX_OPS) return hipErrorInvalidValue;
-    hipEvent_t ev[6] = {};
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &x : ev)
-        if (e == hipSuccess) e = hipEventCreate(&x);
-    auto mark = [&](int k) { return hipEventRecord(ev[k], stream); };
+    StageClock<6> clock(stream);
+    hipError_t e = clock.created;
     const uint64_t n = 1ull << log_n;
-    if (e == hipSuccess) e = mark(0);
+    if (e == hipSuccess) e = clock.mark(0);
     if (e == hipSuccess) e = enqueue_count(d_ops, num_ops, s, stream);
-    if (e == hipSuccess) e = mark(1);
-    if (e == hipSuccess) e = read_header(s, h, stream);
+    if (e == hipSuccess) e = clock.mark(1);
+    if (e == hipSuccess) e = read_status(h, s.header, sizeof(KeccakSpongeTableHeader), stream);
     const bool fill = e == hipSuccess && h->bad_word == KS_NONE && h->bad_span == KS_NONE && h->bad_sum == KS_NONE && (d_bytes || !h->total_bytes) &&
                       fill_arguments_ok(d_ops, num_ops, h->rows, log_n, d_trace, trace_stride);
-    if (e == hipSuccess) e = mark(2);
+    if (e == hipSuccess) e = clock.mark(2);
     if (fill && e == hipSuccess) e = enqueue_map(num_ops, h->rows, s, stream);
-    if (e == hipSuccess) e = mark(3);
+    if (e == hipSuccess) e = clock.mark(3);
     if (fill && e == hipSuccess) e = enqueue_chain(d_ops, num_ops, d_bytes, d_trace, trace_stride, s, stream);
-    if (e == hipSuccess) e = mark(4);
+    if (e == hipSuccess) e = clock.mark(4);
     if (fill && e == hipSuccess) e = enqueue_rows(d_ops, d_bytes, h->rows, n, d_trace, trace_stride, s, stream);
-    if (e == hipSuccess) e = mark(5);
+    if (e == hipSuccess) e = clock.mark(5);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     const int from[4] = {0, 2, 3, 4};  // the wait for the header between the count and the map belongs to no stage
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[from[k]], ev[from[k] + 1]);
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = clock.elapsed(&ms[k], from[k], from[k] + 1);
     return e;
 }
 
@@ -402,11 +393,6 @@ using namespace plonky2_hip;
 
 static_assert(GL_KECCAK_SPONGE_TABLE_COLUMNS == KECCAK_SPONGE_TABLE_COLUMNS && GL_KECCAK_SPONGE_TABLE_OP_WORDS == KECCAK_SPONGE_TABLE_OP_WORDS, "plonky2_hip.h");
 
-static bool ks_bytes_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 static bool ks_shape_ok(uint64_t num_ops, uint32_t degree_bits) {
     return num_ops <= KECCAK_SPONGE_TABLE_MAX_OPS && degree_bits >= 1 && degree_bits <= KECCAK_SPONGE_TABLE_MAX_DEGREE_BITS;
 }
@@ -416,24 +402,24 @@ extern "C" uint64_t gl_keccak_sponge_table_scratch_bytes(uint64_t num_ops, uint3
     return keccak_sponge_table_scratch_layout(nullptr, num_ops, degree_bits).words * 8;
 }
 
-static uint64_t ks_trace_bytes(uint64_t trace_stride, uint64_t n) { return ((uint64_t)(KECCAK_SPONGE_TABLE_COLUMNS - 1) * trace_stride + n) * 8; }
-
 // what is refused before anything is launched; empty: nothing
 static std::string ks_trace_argument_error(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, const uint64_t *d_trace, uint64_t trace_stride,
                                            const void *d_scratch, const void *h_out, const void *ctx) {
     if (!ctx || (num_ops && !d_ops) || !d_scratch || !h_out) return "null pointer";
     if (num_ops > KECCAK_SPONGE_TABLE_MAX_OPS) return "num_ops must be at most 2^30";
-    if (degree_bits == 0 || degree_bits > KECCAK_SPONGE_TABLE_MAX_DEGREE_BITS) return "degree_bits must be in 1 ..= 23";
-    if ((uintptr_t)d_scratch & 15) return "d_scratch must be 16-byte aligned";
+    std::string why = degree_bits_error(degree_bits, KECCAK_SPONGE_TABLE_MAX_DEGREE_BITS);
+    if (why.empty()) why = scratch_alignment_error(d_scratch);
+    if (!why.empty()) return why;
     const uint64_t n = 1ull << degree_bits;
     const uint64_t scratch_bytes = keccak_sponge_table_scratch_layout(nullptr, num_ops, degree_bits).words * 8;
     const uint64_t ops_bytes = num_ops * KECCAK_SPONGE_TABLE_OP_WORDS * 8;
-    if (ks_bytes_overlap(d_ops, ops_bytes, d_scratch, scratch_bytes)) return "d_scratch overlaps d_ops";
+    if (bytes_overlap(d_ops, ops_bytes, d_scratch, scratch_bytes)) return "d_scratch overlaps d_ops";
     if (d_trace) {
-        if (trace_stride < n) return "trace_stride smaller than 2^degree_bits: the columns would overlap";
-        if (trace_stride > (1ull << 40)) return "trace_stride too large";
-        if (ks_bytes_overlap(d_trace, ks_trace_bytes(trace_stride, n), d_ops, ops_bytes)) return "d_trace overlaps d_ops";
-        if (ks_bytes_overlap(d_trace, ks_trace_bytes(trace_stride, n), d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
+        why = trace_stride_error(trace_stride, n);
+        if (!why.empty()) return why;
+        const uint64_t bytes = trace_bytes(KECCAK_SPONGE_TABLE_COLUMNS, trace_stride, n);
+        if (bytes_overlap(d_trace, bytes, d_ops, ops_bytes)) return "d_trace overlaps d_ops";
+        if (bytes_overlap(d_trace, bytes, d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
     }
     return "";
 }
@@ -469,7 +455,7 @@ extern "C" GlError gl_keccak_sponge_table_trace(const uint64_t *d_ops, uint64_t 
     if (h.rows > n)
         return fail(GL_E_INVALID, "gl_keccak_sponge_table_trace: the operations take " + std::to_string(h.rows) +
                                       " rows, more than the 2^degree_bits rows of the trace (the reference would cut an operation in the middle)");
-    if (ks_bytes_overlap(d_trace, ks_trace_bytes(trace_stride, n), d_bytes, h.total_bytes))
+    if (bytes_overlap(d_trace, trace_bytes(KECCAK_SPONGE_TABLE_COLUMNS, trace_stride, n), d_bytes, h.total_bytes))
         return fail(GL_E_INVALID, "gl_keccak_sponge_table_trace: d_trace overlaps d_bytes");
     HIP_TRY(keccak_sponge_table_fill(d_ops, num_ops, d_bytes, h.rows, degree_bits, d_trace, trace_stride, scratch, S(ctx)->stream));
     return ok();
@@ -478,27 +464,25 @@ extern "C" GlError gl_keccak_sponge_table_trace(const uint64_t *d_ops, uint64_t 
 extern "C" GlError gl_keccak_sponge_table_ops(const uint64_t *d_trace, uint64_t trace_stride, uint32_t degree_bits, uint64_t rows, uint64_t *d_keccak_inputs,
                                               uint64_t *d_logic_ops, uint64_t *d_memory_ops, void *d_scratch, void *ctx) {
     DeviceCall device_call(ctx);
-    std::string why;
-    const uint64_t n = degree_bits && degree_bits <= KECCAK_SPONGE_TABLE_MAX_DEGREE_BITS ? 1ull << degree_bits : 0;
-    if (!ctx || !d_trace || !d_scratch) why = "null pointer";
-    else if (!n) why = "degree_bits must be in 1 ..= 23";
-    else if (rows > n) why = "rows exceeds the 2^degree_bits rows of the trace";
-    else if (trace_stride < n) why = "trace_stride smaller than 2^degree_bits: the columns would overlap";
-    else if (trace_stride > (1ull << 40)) why = "trace_stride too large";
-    else if ((uintptr_t)d_scratch & 15) why = "d_scratch must be 16-byte aligned";
-    else {
-        const uint64_t scratch_bytes = keccak_sponge_table_scratch_layout(nullptr, 0, degree_bits).words * 8, trace_bytes = ks_trace_bytes(trace_stride, n);
+    std::string why = !ctx || !d_trace || !d_scratch ? "null pointer" : degree_bits_error(degree_bits, KECCAK_SPONGE_TABLE_MAX_DEGREE_BITS);
+    const uint64_t n = why.empty() ? 1ull << degree_bits : 0;
+    if (why.empty() && rows > n) why = "rows exceeds the 2^degree_bits rows of the trace";
+    if (why.empty()) why = trace_stride_error(trace_stride, n);
+    if (why.empty()) why = scratch_alignment_error(d_scratch);
+    if (why.empty()) {
+        const uint64_t scratch_bytes = keccak_sponge_table_scratch_layout(nullptr, 0, degree_bits).words * 8;
+        const uint64_t trace_bytes = plonky2_hip::trace_bytes(KECCAK_SPONGE_TABLE_COLUMNS, trace_stride, n);
         const uint64_t keccak_bytes = rows * 25 * 8, logic_bytes = rows * 5 * LOGIC_TABLE_OP_WORDS * 8;
         // the memory list's length is known on the device alone: its first record stands for it here
         const uint64_t memory_bytes = rows ? MEMORY_TABLE_OP_WORDS * 8 : 0;
-        if (ks_bytes_overlap(d_trace, trace_bytes, d_scratch, scratch_bytes)) why = "d_trace overlaps d_scratch";
-        else if (ks_bytes_overlap(d_keccak_inputs, keccak_bytes, d_trace, trace_bytes)) why = "d_keccak_inputs overlaps d_trace";
-        else if (ks_bytes_overlap(d_logic_ops, logic_bytes, d_trace, trace_bytes)) why = "d_logic_ops overlaps d_trace";
-        else if (ks_bytes_overlap(d_memory_ops, memory_bytes, d_trace, trace_bytes)) why = "d_memory_ops overlaps d_trace";
-        else if (ks_bytes_overlap(d_keccak_inputs, keccak_bytes, d_scratch, scratch_bytes)) why = "d_keccak_inputs overlaps d_scratch";
-        else if (ks_bytes_overlap(d_logic_ops, logic_bytes, d_scratch, scratch_bytes)) why = "d_logic_ops overlaps d_scratch";
-        else if (ks_bytes_overlap(d_memory_ops, memory_bytes, d_scratch, scratch_bytes)) why = "d_memory_ops overlaps d_scratch";
-        else if (ks_bytes_overlap(d_keccak_inputs, keccak_bytes, d_logic_ops, logic_bytes)) why = "d_keccak_inputs overlaps d_logic_ops";
+        if (bytes_overlap(d_trace, trace_bytes, d_scratch, scratch_bytes)) why = "d_trace overlaps d_scratch";
+        else if (bytes_overlap(d_keccak_inputs, keccak_bytes, d_trace, trace_bytes)) why = "d_keccak_inputs overlaps d_trace";
+        else if (bytes_overlap(d_logic_ops, logic_bytes, d_trace, trace_bytes)) why = "d_logic_ops overlaps d_trace";
+        else if (bytes_overlap(d_memory_ops, memory_bytes, d_trace, trace_bytes)) why = "d_memory_ops overlaps d_trace";
+        else if (bytes_overlap(d_keccak_inputs, keccak_bytes, d_scratch, scratch_bytes)) why = "d_keccak_inputs overlaps d_scratch";
+        else if (bytes_overlap(d_logic_ops, logic_bytes, d_scratch, scratch_bytes)) why = "d_logic_ops overlaps d_scratch";
+        else if (bytes_overlap(d_memory_ops, memory_bytes, d_scratch, scratch_bytes)) why = "d_memory_ops overlaps d_scratch";
+        else if (bytes_overlap(d_keccak_inputs, keccak_bytes, d_logic_ops, logic_bytes)) why = "d_keccak_inputs overlaps d_logic_ops";
     }
     if (!why.empty()) return fail(GL_E_INVALID, "gl_keccak_sponge_table_ops: " + why);
     HIP_TRY(keccak_sponge_table_derive(d_trace, trace_stride, rows, d_keccak_inputs, d_logic_ops, d_memory_ops,
@@ -519,4 +503,126 @@ extern "C" GlError gl_debug_keccak_sponge_table_stage_ms(const uint64_t *d_ops, 
     if (bad.empty() && (h.rows > (1ull << degree_bits) || (h.total_bytes && !d_bytes))) bad = "the rows do not fit the trace or d_bytes is missing";
     if (!bad.empty()) return fail(GL_E_INVALID, "gl_debug_keccak_sponge_table_stage_ms: nothing was filled: " + bad);
     return ok();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the Keccak sponge table as ONE STARK program: plonky2_gpu_amd/keccak_sponge_table.py program(), call for call
+// (tests/test_keccak_sponge_table_ref.py holds the two against each other word for word). The reference's eval_packed_generic for
+// this table is a list of TODOs (evm/src/keccak_sponge/keccak_sponge_stark.rs:363-377); this is that list written out, in its
+// order — the reference's to-do list, not a soundness claim: nothing here ties xored_rate_u32s to the block, for example, which
+// is the logic lookup's job. "before_rate_bits" and "block_bits" name columns the layout does not have; nothing is emitted for them.
+// Host code; the columns are keccak_sponge_table.h's (the 16 of original_capacity_u32s follow the 34 of original_rate_u32s).
+namespace {
+
+using namespace plonky2_hip::program_asm;
+
+Program keccak_sponge_table_program(ImmediatePool &pool) {
+    constexpr int RATE_BYTES = KECCAK_SPONGE_RATE_BYTES, WIDTH_U32S = KECCAK_SPONGE_WIDTH_U32S;
+    StarkAsm a(&pool);
+    auto boolean = [&](int column) {
+        a.release();
+        const int flag = a.local(column);
+        const int one = a.imm(1);
+        const int t = a.sub(flag, one);
+        a.emit(a.mul(flag, t));
+    };
+    // each flag is boolean, and so is the implied dummy flag 1 - F - L: F L = 0
+    boolean(KS_IS_FULL_INPUT_BLOCK);
+    boolean(KS_IS_FINAL_BLOCK);
+    {
+        a.release();
+        const int full = a.local(KS_IS_FULL_INPUT_BLOCK);
+        const int fin = a.local(KS_IS_FINAL_BLOCK);
+        a.emit(a.mul(full, fin));
+    }
+    // is_final_input_len contains booleans
+    for (int i = 0; i < RATE_BYTES; i++) boolean(KS_IS_FINAL_INPUT_LEN + i);
+    // their sum equals is_final_block
+    {
+        a.release();
+        for (int i = 0; i < RATE_BYTES; i++) {
+            const int t = a.local(KS_IS_FINAL_INPUT_LEN + i);
+            a.acc(t, 1);
+            a.free1(t);
+        }
+        const int sum = a.accr();
+        const int fin = a.local(KS_IS_FINAL_BLOCK);
+        a.emit(a.sub(sum, fin));
+    }
+    // the columns that are zero where a sponge starts: the original state, then already_absorbed_bytes
+    int fresh[WIDTH_U32S + 1];
+    for (int j = 0; j < WIDTH_U32S; j++) fresh[j] = KS_ORIGINAL_RATE_U32S + j;
+    fresh[WIDTH_U32S] = KS_ALREADY_ABSORBED_BYTES;
+    // the first row starts a sponge
+    for (int column : fresh) {
+        a.release();
+        a.emit_first_row(a.local(column));
+    }
+    // behind a final block the next row starts one
+    for (int column : fresh) {
+        a.release();
+        const int fin = a.local(KS_IS_FINAL_BLOCK);
+        const int nxt = a.next(column);
+        a.emit_transition(a.mul(fin, nxt));
+    }
+    // behind a full-input block the next row's address, time and len match
+    for (int column : {KS_CONTEXT, KS_SEGMENT, KS_VIRT, KS_TIMESTAMP, KS_LEN}) {
+        a.release();
+        const int full = a.local(KS_IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(column);
+        const int local = a.local(column);
+        const int diff = a.sub(nxt, local);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // ... its "before" is our "after"
+    for (int j = 0; j < WIDTH_U32S; j++) {
+        a.release();
+        const int full = a.local(KS_IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(KS_ORIGINAL_RATE_U32S + j);
+        const int updated = a.local(KS_UPDATED_STATE_U32S + j);
+        const int diff = a.sub(nxt, updated);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // ... and its already_absorbed_bytes is ours plus 136
+    {
+        a.release();
+        const int full = a.local(KS_IS_FULL_INPUT_BLOCK);
+        const int nxt = a.next(KS_ALREADY_ABSORBED_BYTES);
+        const int local = a.local(KS_ALREADY_ABSORBED_BYTES);
+        const int diff = a.sub(nxt, local);
+        const int rate = a.imm(RATE_BYTES);
+        a.sub(diff, rate, diff);
+        a.emit_transition(a.mul(full, diff));
+    }
+    // a dummy row is followed by a dummy row
+    {
+        a.release();
+        const int dummy = a.imm(1);
+        const int full = a.local(KS_IS_FULL_INPUT_BLOCK);
+        a.sub(dummy, full, dummy);
+        const int fin = a.local(KS_IS_FINAL_BLOCK);
+        a.sub(dummy, fin, dummy);
+        const int next_full = a.next(KS_IS_FULL_INPUT_BLOCK);
+        const int next_fin = a.next(KS_IS_FINAL_BLOCK);
+        const int next_used = a.add(next_full, next_fin);
+        a.emit_transition(a.mul(dummy, next_used));
+    }
+    // is_final_input_len[i] implies len - already_absorbed_bytes == i
+    for (int i = 0; i < RATE_BYTES; i++) {
+        a.release();
+        const int flag = a.local(KS_IS_FINAL_INPUT_LEN + i);
+        const int len = a.local(KS_LEN);
+        const int absorbed = a.local(KS_ALREADY_ABSORBED_BYTES);
+        const int diff = a.sub(len, absorbed);
+        const int index = a.imm(i);
+        a.sub(diff, index, diff);
+        a.emit(a.mul(flag, diff));
+    }
+    return a.instrs;
+}
+
+}  // namespace
+
+extern "C" GlError gl_keccak_sponge_table_program(GlGatePrograms *out) {
+    return emit_table_program("gl_keccak_sponge_table_program", keccak_sponge_table_program, out);
 }

@@ -16,6 +16,8 @@
 #include "keccak_table.h"
 
 #include "ctx.h"
+#include "program_asm.h"
+#include "table_args.h"
 
 namespace plonky2_hip {
 
@@ -125,17 +127,160 @@ extern "C" GlError gl_keccak_table_trace(const uint64_t *d_inputs, uint64_t num_
                                          uint64_t trace_stride, void *ctx) {
     DeviceCall device_call(ctx);
     if (!ctx || !d_trace || (num_inputs && !d_inputs)) return fail(GL_E_INVALID, "gl_keccak_table_trace: null pointer");
-    if (degree_bits == 0 || degree_bits > 24) return fail(GL_E_INVALID, "gl_keccak_table_trace: degree_bits must be in 1 ..= 24");
+    std::string why = degree_bits_error(degree_bits, 24);
+    if (!why.empty()) return fail(GL_E_INVALID, "gl_keccak_table_trace: " + why);
     const uint64_t n = 1ull << degree_bits;
     if (num_inputs > n / KECCAK_TABLE_ROUNDS)
         return fail(GL_E_INVALID, "gl_keccak_table_trace: 24 * num_inputs exceeds the 2^degree_bits rows of the trace");
-    if (trace_stride < n) return fail(GL_E_INVALID, "gl_keccak_table_trace: trace_stride smaller than 2^degree_bits: the columns would overlap");
-    if (trace_stride > (1ull << 40)) return fail(GL_E_INVALID, "gl_keccak_table_trace: trace_stride too large");
-    if (num_inputs) {
-        const uintptr_t t0 = (uintptr_t)d_trace, t1 = t0 + ((uint64_t)(KECCAK_TABLE_COLUMNS - 1) * trace_stride + n) * 8;
-        const uintptr_t i0 = (uintptr_t)d_inputs, i1 = i0 + num_inputs * 25 * 8;
-        if (t0 < i1 && i0 < t1) return fail(GL_E_INVALID, "gl_keccak_table_trace: d_trace overlaps d_inputs");
-    }
+    why = trace_stride_error(trace_stride, n);
+    if (!why.empty()) return fail(GL_E_INVALID, "gl_keccak_table_trace: " + why);
+    if (bytes_overlap(d_trace, trace_bytes(KECCAK_TABLE_COLUMNS, trace_stride, n), d_inputs, num_inputs * 25 * 8))
+        return fail(GL_E_INVALID, "gl_keccak_table_trace: d_trace overlaps d_inputs");
     HIP_TRY(keccak_table_trace(d_inputs, num_inputs, degree_bits, d_trace, trace_stride, S(ctx)->stream));
     return ok();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's Keccak-f table (evm/src/keccak/keccak_stark.rs:230-375 with round_flags.rs:12-27 and
+// logic.rs) as ONE STARK program: plonky2_gpu_amd/keccak_table.py program(), call for call (tests/test_keccak_table_ref.py holds
+// the two against each other word for word). Host code; the columns are keccak_table.h's.
+namespace {
+
+using namespace plonky2_hip::program_asm;
+
+Program keccak_table_program(ImmediatePool &pool) {
+    constexpr int NUM_ROUNDS = KECCAK_TABLE_ROUNDS;
+    StarkAsm a(&pool);
+    // eval_round_flags
+    {
+        const int s0 = a.local(kt_reg_step(0));
+        const int one = a.imm(1);
+        a.emit_first_row(a.sub(s0, one));
+    }
+    for (int i = 1; i < NUM_ROUNDS; i++) {
+        a.release();
+        a.emit_first_row(a.local(kt_reg_step(i)));
+    }
+    for (int i = 0; i < NUM_ROUNDS; i++) {
+        a.release();
+        const int nx = a.next(kt_reg_step((i + 1) % NUM_ROUNDS));
+        const int lc = a.local(kt_reg_step(i));
+        a.emit_transition(a.sub(nx, lc));
+    }
+    // C'[x, z] = xor(C[x, z], C[x - 1, z], C[x + 1, z - 1])
+    for (int x = 0; x < 5; x++)
+        for (int z = 0; z < 64; z++) {
+            a.release();
+            const int c0 = a.local(kt_reg_c(x, z));
+            const int c1 = a.local(kt_reg_c((x + 4) % 5, z));
+            const int c2 = a.local(kt_reg_c((x + 1) % 5, (z + 63) % 64));
+            const int x3 = a.xor3(c0, c1, c2);
+            const int cp = a.local(kt_reg_c_prime(x, z));
+            a.emit(a.sub(cp, x3));
+        }
+    // A[x, y, z] = xor(A'[x, y, z], C[x, z], C'[x, z]), recomposed into the two input limbs
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++) {
+            auto bit = [&](int z) {
+                const int ap = a.local(kt_reg_a_prime(x, y, z));
+                const int c = a.local(kt_reg_c(x, z));
+                const int cp = a.local(kt_reg_c_prime(x, z));
+                const int t = a.xor3(ap, c, cp);
+                a.free({ap, c, cp});
+                return t;
+            };
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int computed = a.limb(bit, 32 * l);
+                const int al = a.local(kt_reg_a(x, y) + l);
+                a.emit(a.sub(computed, al));
+            }
+        }
+    // diff (diff - 2) (diff - 4) = 0 with diff = sum_i A'[x, i, z] - C'[x, z]
+    for (int x = 0; x < 5; x++)
+        for (int z = 0; z < 64; z++) {
+            a.release();
+            const int s = a.local(kt_reg_a_prime(x, 0, z));
+            for (int i = 1; i < 5; i++) {
+                const int t = a.local(kt_reg_a_prime(x, i, z));
+                a.add(s, t, s);
+                a.free1(t);
+            }
+            const int cp = a.local(kt_reg_c_prime(x, z));
+            const int diff = a.sub(s, cp);
+            const int two = a.imm(2);
+            const int d2 = a.sub(diff, two);
+            const int four = a.imm(4);
+            const int d4 = a.sub(diff, four);
+            const int m = a.mul(diff, d2);
+            a.emit(a.mul(m, d4));
+        }
+    // A''[x, y] = xor(B[x, y], andn(B[x + 1, y], B[x + 2, y]))
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++)
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int one = a.imm(1);
+                auto bit = [&](int z) {
+                    const int b0 = a.local(kt_reg_b(x, y, z));
+                    const int b1 = a.local(kt_reg_b((x + 1) % 5, y, z));
+                    const int b2 = a.local(kt_reg_b((x + 2) % 5, y, z));
+                    const int n = a.sub(one, b1);
+                    a.mul(n, b2, n);  // andn_gen(x, y) = (1 - x) y
+                    const int t = a.xor2(b0, n);
+                    a.free({b0, b1, b2, n});
+                    return t;
+                };
+                const int computed = a.limb(bit, 32 * l);
+                const int app = a.local(kt_reg_a_prime_prime(x, y) + l);
+                a.emit(a.sub(computed, app));
+            }
+    // A'''[0, 0] = A''[0, 0] xor RC: the bits of A''[0, 0] recompose into its limbs ...
+    for (int l = 0; l < 2; l++) {
+        a.release();
+        const int computed = a.limb([&](int z) { return a.local(kt_reg_a_prime_prime_0_0_bit(z)); }, 32 * l);
+        const int app = a.local(kt_reg_a_prime_prime(0, 0) + l);
+        a.emit(a.sub(computed, app));
+    }
+    // ... and xored with the round's constant into the limbs of A'''[0, 0]
+    auto xored_bit = [&](int i) {
+        const int b = a.local(kt_reg_a_prime_prime_0_0_bit(i));
+        bool any = false;
+        for (int r = 0; r < NUM_ROUNDS; r++)
+            if ((KT_ROUND_CONSTANTS[r] >> i) & 1) {
+                const int f = a.local(kt_reg_step(r));
+                a.acc(f, 1, 1);
+                a.free1(f);
+                any = true;
+            }
+        if (!any) return b;
+        const int rc = a.accr(1);
+        const int t = a.xor2(b, rc);
+        a.free({b, rc});
+        return t;
+    };
+    for (int l = 0; l < 2; l++) {
+        a.release();
+        const int computed = a.limb(xored_bit, 32 * l);
+        const int appp = a.local(kt_reg_a_prime_prime_prime(0, 0) + l);
+        a.emit(a.sub(computed, appp));
+    }
+    // this round's output is the next round's input, except behind the last round
+    for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++)
+            for (int l = 0; l < 2; l++) {
+                a.release();
+                const int one = a.imm(1);
+                const int last = a.local(kt_reg_step(NUM_ROUNDS - 1));
+                const int not_last = a.sub(one, last);
+                const int out = a.local(kt_reg_a_prime_prime_prime(x, y) + l);
+                const int in = a.next(kt_reg_a(x, y) + l);
+                const int diff = a.sub(out, in);
+                a.emit_transition(a.mul(not_last, diff));
+            }
+    return a.instrs;
+}
+
+}  // namespace
+
+extern "C" GlError gl_keccak_table_program(GlGatePrograms *out) { return emit_table_program("gl_keccak_table_program", keccak_table_program, out); }

@@ -9,6 +9,7 @@ namespace plonky2_hip {
 constexpr uint32_t LOGIC_TABLE_COLUMNS = 523;
 constexpr uint32_t LOGIC_TABLE_OP_WORDS = 17;  // the operator, the eight limbs of input0, the eight limbs of input1
 constexpr uint32_t LOGIC_TABLE_LIMBS = 8;
+constexpr uint32_t LOGIC_TABLE_VAL_BITS = 32 * LOGIC_TABLE_LIMBS;  // the bit columns of one input
 constexpr uint32_t LOGIC_TABLE_THREADS = 256;
 constexpr uint32_t LOGIC_TABLE_MAX_DEGREE_BITS = 23;  // gl_stark_create: degree_bits + rate_bits <= 24, and degree 3 needs rate_bits >= 1
 

@@ -20,6 +20,8 @@
 #include <string>
 
 #include "ctx.h"
+#include "program_asm.h"
+#include "table_args.h"
 
 namespace plonky2_hip {
 
@@ -114,9 +116,7 @@ hipError_t logic_table_validate(const uint64_t *d_ops, uint64_t num_ops, LogicTa
     lt_validate<<<dim3((unsigned)((words + T - 1) / T)), dim3(T), 0, stream>>>(d_ops, words, d_status);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(h, d_status, sizeof(LogicTableStatus), hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
+    return read_status(h, d_status, sizeof(LogicTableStatus), stream);
 }
 
 hipError_t logic_table_fill(const uint64_t *d_ops, uint64_t num_ops, uint32_t log_n, uint64_t *d_trace, uint64_t trace_stride,
@@ -140,27 +140,23 @@ static_assert(GL_LOGIC_TABLE_COLUMNS == LOGIC_TABLE_COLUMNS && GL_LOGIC_TABLE_OP
                   GL_LOGIC_TABLE_SCRATCH_BYTES == sizeof(LogicTableStatus),
               "plonky2_hip.h");
 
-static bool logic_table_bytes_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 // what is refused before anything is launched; empty: nothing. d_scratch is checked where `with_scratch`.
 static std::string logic_table_argument_error(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, const uint64_t *d_trace,
                                               uint64_t trace_stride, const void *d_scratch, bool with_scratch, const void *ctx) {
     if (!ctx || !d_trace || (num_ops && !d_ops) || (with_scratch && !d_scratch)) return "null pointer";
-    if (degree_bits == 0 || degree_bits > LOGIC_TABLE_MAX_DEGREE_BITS) return "degree_bits must be in 1 ..= 23";
+    std::string why = degree_bits_error(degree_bits, LOGIC_TABLE_MAX_DEGREE_BITS);
+    if (!why.empty()) return why;
     const uint64_t n = 1ull << degree_bits;
     if (num_ops > n) return "num_ops exceeds the 2^degree_bits rows of the trace";
-    if (trace_stride < n) return "trace_stride smaller than 2^degree_bits: the columns would overlap";
-    if (trace_stride > (1ull << 40)) return "trace_stride too large";
-    if (with_scratch && ((uintptr_t)d_scratch & 15)) return "d_scratch must be 16-byte aligned";
+    why = trace_stride_error(trace_stride, n);
+    if (why.empty() && with_scratch) why = scratch_alignment_error(d_scratch);
+    if (!why.empty()) return why;
     const uint64_t ops_bytes = num_ops * LOGIC_TABLE_OP_WORDS * 8;
-    const uint64_t trace_bytes = ((uint64_t)(LOGIC_TABLE_COLUMNS - 1) * trace_stride + n) * 8;
+    const uint64_t bytes = trace_bytes(LOGIC_TABLE_COLUMNS, trace_stride, n);
     const uint64_t scratch_bytes = with_scratch ? sizeof(LogicTableStatus) : 0;
-    if (logic_table_bytes_overlap(d_trace, trace_bytes, d_ops, ops_bytes)) return "d_trace overlaps d_ops";
-    if (logic_table_bytes_overlap(d_scratch, scratch_bytes, d_ops, ops_bytes)) return "d_scratch overlaps d_ops";
-    if (logic_table_bytes_overlap(d_trace, trace_bytes, d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
+    if (bytes_overlap(d_trace, bytes, d_ops, ops_bytes)) return "d_trace overlaps d_ops";
+    if (bytes_overlap(d_scratch, scratch_bytes, d_ops, ops_bytes)) return "d_scratch overlaps d_ops";
+    if (bytes_overlap(d_trace, bytes, d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
     return "";
 }
 
@@ -193,3 +189,57 @@ extern "C" GlError gl_debug_logic_table_fill(const uint64_t *d_ops, uint64_t num
     HIP_TRY(logic_table_fill(d_ops, num_ops, degree_bits, d_trace, trace_stride, rows_per_thread, S(ctx)->stream));
     return ok();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's logic table (evm/src/logic.rs:182-231) as ONE STARK program:
+// plonky2_gpu_amd/logic_table.py program(), call for call (tests/test_logic_table_ref.py holds the two against each other word
+// for word). Host code; the columns are logic_table.h's.
+namespace {
+
+using namespace plonky2_hip::program_asm;
+
+Program logic_table_program(ImmediatePool &pool) {
+    StarkAsm a(&pool);
+    // all bits are indeed bits
+    for (int start : {LT_INPUT0, LT_INPUT1})
+        for (int i = 0; i < (int)LOGIC_TABLE_VAL_BITS; i++) {
+            a.release();
+            const int bit = a.local(start + i);
+            const int one = a.imm(1);
+            const int t = a.sub(bit, one);
+            a.emit(a.mul(bit, t));
+        }
+    // RESULT[i] = sum_coeff (x + y) + and_coeff (x AND y) on the limb's 32 bits
+    for (int i = 0; i < (int)LOGIC_TABLE_LIMBS; i++) {
+        a.release();
+        const int x = a.limb([&](int z) { return a.local(LT_INPUT0 + z); }, 32 * i);
+        const int y = a.limb([&](int z) { return a.local(LT_INPUT1 + z); }, 32 * i);
+        const int x_land_y = a.limb(
+            [&](int z) {
+                const int x_bit = a.local(LT_INPUT0 + z);
+                const int y_bit = a.local(LT_INPUT1 + z);
+                a.mul(x_bit, y_bit, x_bit);
+                a.free1(y_bit);
+                return x_bit;
+            },
+            32 * i);
+        const int is_and = a.local(LT_IS_AND);
+        const int is_or = a.local(LT_IS_OR);
+        const int is_xor = a.local(LT_IS_XOR);
+        const int sum_coeff = a.add(is_or, is_xor);
+        const int and_coeff = a.sub(is_and, is_or);
+        a.mulk(is_xor, 1, is_xor);
+        a.sub(and_coeff, is_xor, and_coeff);
+        a.add(x, y, x);
+        a.mul(sum_coeff, x, x);
+        a.mul(and_coeff, x_land_y, x_land_y);
+        a.add(x, x_land_y, x);
+        const int result = a.local(LT_RESULT + i);
+        a.emit(a.sub(result, x));
+    }
+    return a.instrs;
+}
+
+}  // namespace
+
+extern "C" GlError gl_logic_table_program(GlGatePrograms *out) { return emit_table_program("gl_logic_table_program", logic_table_program, out); }

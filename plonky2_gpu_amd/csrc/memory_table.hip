@@ -23,6 +23,8 @@
 #include <string>
 
 #include "ctx.h"
+#include "program_asm.h"
+#include "table_args.h"
 
 namespace plonky2_hip {
 
@@ -208,12 +210,6 @@ hipError_t enqueue_gaps(const uint64_t *d_ops, uint64_t num_ops, uint64_t n, con
     return hipGetLastError();
 }
 
-hipError_t read_header(const MemoryTableScratch &s, MemoryTableHeader *h, hipStream_t stream) {
-    hipError_t e = hipMemcpyAsync(h, s.header, sizeof(MemoryTableHeader), hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
-}
-
 hipError_t enqueue_rows(const uint64_t *d_ops, uint64_t num_ops, uint32_t log_n, uint64_t *d_trace, uint64_t trace_stride, const MemoryTableScratch &s,
                         hipStream_t stream) {
     const uint64_t n = 1ull << log_n;
@@ -242,7 +238,7 @@ hipError_t memory_table_count(const uint64_t *d_ops, uint64_t num_ops, uint64_t 
     if (e != hipSuccess) return e;
     e = enqueue_gaps(d_ops, num_ops, n, s, stream);
     if (e != hipSuccess) return e;
-    return read_header(s, h, stream);
+    return read_status(h, s.header, sizeof(MemoryTableHeader), stream);
 }
 
 hipError_t memory_table_fill(const uint64_t *d_ops, uint64_t num_ops, uint32_t log_n, uint64_t *d_trace, uint64_t trace_stride,
@@ -257,42 +253,32 @@ hipError_t memory_table_fill(const uint64_t *d_ops, uint64_t num_ops, uint32_t l
 
 hipError_t memory_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, uint32_t log_n, uint64_t *d_trace, uint64_t trace_stride,
                                  const MemoryTableScratch &s, MemoryTableHeader *h, float *ms, hipStream_t stream) {
-    hipEvent_t ev[7] = {};
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &x : ev)
-        if (e == hipSuccess) e = hipEventCreate(&x);
-    auto mark = [&](int k) { return hipEventRecord(ev[k], stream); };
+    StageClock<7> clock(stream);
+    hipError_t e = clock.created;
     const uint64_t n = 1ull << log_n;
-    if (e == hipSuccess) e = mark(0);
+    if (e == hipSuccess) e = clock.mark(0);
     if (e == hipSuccess) e = enqueue_sort(d_ops, num_ops, s, stream);
-    if (e == hipSuccess) e = mark(1);
+    if (e == hipSuccess) e = clock.mark(1);
     if (e == hipSuccess) e = enqueue_gaps(d_ops, num_ops, n, s, stream);
-    if (e == hipSuccess) e = mark(2);
-    if (e == hipSuccess) e = read_header(s, h, stream);
+    if (e == hipSuccess) e = clock.mark(2);
+    if (e == hipSuccess) e = read_status(h, s.header, sizeof(MemoryTableHeader), stream);
     const bool fill = e == hipSuccess && h->status == 0;
-    if (e == hipSuccess) e = mark(3);
+    if (e == hipSuccess) e = clock.mark(3);
     if (fill && e == hipSuccess) e = enqueue_rows(d_ops, num_ops, log_n, d_trace, trace_stride, s, stream);
-    if (e == hipSuccess) e = mark(4);
+    if (e == hipSuccess) e = clock.mark(4);
     if (fill && e == hipSuccess) e = enqueue_flags(log_n, d_trace, trace_stride, s, stream);
-    if (e == hipSuccess) e = mark(5);
+    if (e == hipSuccess) e = clock.mark(5);
     if (fill && e == hipSuccess) e = enqueue_lookup(log_n, d_trace, trace_stride, s, stream);
-    if (e == hipSuccess) e = mark(6);
+    if (e == hipSuccess) e = clock.mark(6);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     const int from[5] = {0, 1, 3, 4, 5};  // the wait for the header between the gaps and the rows belongs to no stage
-    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[from[k]], ev[from[k] + 1]);
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = clock.elapsed(&ms[k], from[k], from[k] + 1);
     return e;
 }
 
 }  // namespace plonky2_hip
 
 using namespace plonky2_hip;
-
-static bool bytes_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
 
 static bool memory_table_shape_ok(uint64_t num_ops, uint32_t degree_bits) {
     return num_ops >= 2 && num_ops <= MEMORY_TABLE_MAX_OPS && degree_bits >= 1 && degree_bits <= MEMORY_TABLE_MAX_DEGREE_BITS;
@@ -308,18 +294,19 @@ static std::string memory_table_argument_error(const uint64_t *d_ops, uint64_t n
                                                uint64_t trace_stride, const void *d_scratch, const void *h_out, const void *ctx) {
     if (!ctx || !d_ops || !d_scratch || !h_out) return "null pointer";
     if (num_ops < 2 || num_ops > MEMORY_TABLE_MAX_OPS) return "num_ops must be in 2 ..= 2^30";
-    if (degree_bits == 0 || degree_bits > MEMORY_TABLE_MAX_DEGREE_BITS) return "degree_bits must be in 1 ..= 23";
-    if ((uintptr_t)d_scratch & 15) return "d_scratch must be 16-byte aligned";
+    std::string why = degree_bits_error(degree_bits, MEMORY_TABLE_MAX_DEGREE_BITS);
+    if (why.empty()) why = scratch_alignment_error(d_scratch);
+    if (!why.empty()) return why;
     const uint64_t n = 1ull << degree_bits;
     const uint64_t scratch_bytes = memory_table_scratch_layout(nullptr, num_ops, degree_bits).words * 8;
     const uint64_t ops_bytes = num_ops * MEMORY_TABLE_OP_WORDS * 8;
     if (bytes_overlap(d_ops, ops_bytes, d_scratch, scratch_bytes)) return "d_scratch overlaps d_ops";
     if (d_trace) {
-        if (trace_stride < n) return "trace_stride smaller than 2^degree_bits: the columns would overlap";
-        if (trace_stride > (1ull << 40)) return "trace_stride too large";
-        const uint64_t trace_bytes = ((uint64_t)(MEMORY_TABLE_COLUMNS - 1) * trace_stride + n) * 8;
-        if (bytes_overlap(d_trace, trace_bytes, d_ops, ops_bytes)) return "d_trace overlaps d_ops";
-        if (bytes_overlap(d_trace, trace_bytes, d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
+        why = trace_stride_error(trace_stride, n);
+        if (!why.empty()) return why;
+        const uint64_t bytes = trace_bytes(MEMORY_TABLE_COLUMNS, trace_stride, n);
+        if (bytes_overlap(d_trace, bytes, d_ops, ops_bytes)) return "d_trace overlaps d_ops";
+        if (bytes_overlap(d_trace, bytes, d_scratch, scratch_bytes)) return "d_trace overlaps d_scratch";
     }
     return "";
 }
@@ -364,3 +351,101 @@ extern "C" GlError gl_debug_memory_table_stage_ms(const uint64_t *d_ops, uint64_
                                   h_ms, S(ctx)->stream));
     return h.status ? memory_table_data_error(h) : ok();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The constraints of the reference's memory table (evm/src/memory/memory_stark.rs:242-319 with lookup.rs:19-33) as ONE STARK
+// program: plonky2_gpu_amd/memory_table.py program(), call for call (tests/test_memory_table_ref.py holds the two against each
+// other word for word). Host code; the columns are memory_table.h's.
+namespace {
+
+using namespace plonky2_hip::program_asm;
+
+Program memory_table_program(ImmediatePool &pool) {
+    StarkAsm a(&pool);
+    const int one = a.imm(1);
+    // the filter is 0 or 1
+    const int filter = a.local(MT_FILTER);
+    {
+        const int t = a.sub(filter, one);
+        a.mul(filter, t, t);
+        a.emit(t);
+        a.free1(t);
+    }
+    // a dummy row (filter off) is a read
+    {
+        const int is_dummy = a.sub(one, filter);
+        const int is_read = a.local(MT_IS_READ);
+        const int is_write = a.sub(one, is_read);
+        const int t = a.mul(is_dummy, is_write);
+        a.emit(t);
+        a.free({t, is_dummy, is_write, is_read, filter});
+    }
+    // first set of ordering constraints: the first_change flags and address_unchanged are boolean
+    const int context_first_change = a.local(MT_CONTEXT_FIRST_CHANGE);
+    const int segment_first_change = a.local(MT_SEGMENT_FIRST_CHANGE);
+    const int virtual_first_change = a.local(MT_VIRTUAL_FIRST_CHANGE);
+    const int address_unchanged = a.sub(one, context_first_change);
+    a.sub(address_unchanged, segment_first_change, address_unchanged);
+    a.sub(address_unchanged, virtual_first_change, address_unchanged);
+    for (int flag : {context_first_change, segment_first_change, virtual_first_change, address_unchanged}) {
+        const int t = a.sub(one, flag);
+        a.mul(flag, t, t);
+        a.emit(t);
+        a.free1(t);
+    }
+    // second set: no change before the column of the flag that is set
+    int diffs[4];
+    const int diff_columns[4] = {MT_ADDR_CONTEXT, MT_ADDR_SEGMENT, MT_ADDR_VIRTUAL, MT_TIMESTAMP};
+    for (int k = 0; k < 4; k++) {
+        const int nxt = a.next(diff_columns[k]);
+        const int local = a.local(diff_columns[k]);
+        a.sub(nxt, local, nxt);
+        a.free1(local);
+        diffs[k] = nxt;
+    }
+    const int d_context = diffs[0], d_segment = diffs[1], d_virtual = diffs[2], d_timestamp = diffs[3];
+    const int transitions[6][2] = {{segment_first_change, d_context}, {virtual_first_change, d_context}, {virtual_first_change, d_segment},
+                                   {address_unchanged, d_context},    {address_unchanged, d_segment},    {address_unchanged, d_virtual}};
+    for (const auto &fd : transitions) {
+        const int t = a.mul(fd[0], fd[1]);
+        a.emit_transition(t);
+        a.free1(t);
+    }
+    // third set: the range check is the difference of the column that should be increasing
+    {
+        const int computed = a.sub(d_context, one);
+        a.mul(context_first_change, computed, computed);
+        const int terms[2][2] = {{segment_first_change, d_segment}, {virtual_first_change, d_virtual}};
+        for (const auto &fd : terms) {
+            const int t = a.sub(fd[1], one);
+            a.mul(fd[0], t, t);
+            a.add(computed, t, computed);
+            a.free1(t);
+        }
+        const int t = a.mul(address_unchanged, d_timestamp);
+        a.add(computed, t, computed);
+        a.free1(t);
+        const int range_check = a.local(MT_RANGE_CHECK);
+        a.sub(range_check, computed, computed);
+        a.emit_transition(computed);
+        a.free({computed, range_check});
+    }
+    // the purportedly ordered log: a read of an unchanged address sees the value of the row before
+    const int gate = a.next(MT_IS_READ);
+    a.mul(gate, address_unchanged, gate);
+    for (int i = 0; i < 8; i++) {
+        const int nxt = a.next(MT_VALUE_START + i);
+        const int local = a.local(MT_VALUE_START + i);
+        a.sub(nxt, local, nxt);
+        a.mul(gate, nxt, nxt);
+        a.emit(nxt);
+        a.free({nxt, local});
+    }
+    a.release();
+    a.eval_lookups(MT_RANGE_CHECK_PERMUTED, MT_COUNTER_PERMUTED);
+    return a.instrs;
+}
+
+}  // namespace
+
+extern "C" GlError gl_memory_table_program(GlGatePrograms *out) { return emit_table_program("gl_memory_table_program", memory_table_program, out); }

@@ -1,6 +1,6 @@
 // program_isa.h — the register-program instruction set, once: GlGateInstr {op, dst, a, b} of include/plonky2_hip.h as the gate
-// programs (plonk.hip, gate_jit.hip) and the STARK programs (stark.hip, stark_jit.hip) use it and gate_emit.hip writes it. 0..10 are
-// common to both (1 is invalid in a STARK program), 11..14 STARK only. What a consumer accepts and says stays with it.
+// programs (plonk.hip, gate_jit.hip) and the STARK programs (stark.hip, stark_jit.hip) use it and program_asm.h's assemblers write it
+// (gate_emit.hip: gates; <table>.hip: a table's program). 0..10 are common to both (1 is invalid in a STARK program), 11..14 STARK only.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -26,7 +26,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, table
 from .device import DeviceBuffer
 from .stark import CtlColumn, StarkAsm, StarkDesc
 
@@ -159,17 +159,7 @@ def stark_desc(degree_bits, num_challenges, fri_params):
 def native_program():
     """gl_keccak_sponge_table_program: (instrs, immediates, number of constraints) as the library emits them — program() word for
     word"""
-    out = _lib.GlGatePrograms()
-    _lib.call("gl_keccak_sponge_table_program", ctypes.byref(out))
-    try:
-        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
-        imms = [int(v) for v in np.ctypeslib.as_array(ctypes.cast(out.immediates, ctypes.POINTER(ctypes.c_uint64)), shape=(out.num_immediates,))]
-        if out.gates or out.num_gates:
-            raise RuntimeError("gl_keccak_sponge_table_program: a STARK program has no gate descriptors")
-        return instrs, imms, int(out.num_gate_constraints)
-    finally:
-        _lib.load().gl_gate_programs_free(ctypes.byref(out))
-
+    return table.native_program("gl_keccak_sponge_table_program")
 
 # ---------------------------------------------------------------- the lookups (keccak_sponge_stark.rs:26-146)
 def ctl_looked_data():
@@ -264,12 +254,7 @@ def upload_bytes(ctx, data, offset=0):
 
 def _device_ops(ctx, ops, data):
     """(records DeviceBuffer or None, num_ops, bytes DeviceBuffer or None, address of the first byte or None)"""
-    if isinstance(ops, DeviceBuffer):
-        d_ops, num_ops = ops, ops.n // OP_WORDS
-    else:
-        host = np.ascontiguousarray(np.asarray(ops, dtype=np.uint64).reshape(-1, OP_WORDS))
-        num_ops = host.shape[0]
-        d_ops = DeviceBuffer.from_host(ctx, host) if num_ops else None
+    d_ops, num_ops = table.device_records(ctx, ops, OP_WORDS)
     if data is None or isinstance(data, int):
         return d_ops, num_ops, None, data
     if isinstance(data, DeviceBuffer):
@@ -282,17 +267,14 @@ def _device_ops(ctx, ops, data):
 
 
 def _scratch(ctx, num_ops, degree_bits):
-    size = _lib.load().gl_keccak_sponge_table_scratch_bytes(num_ops, degree_bits)
-    if not size:
-        raise ValueError("gl_keccak_sponge_table_scratch_bytes: num_ops must be at most 2^30 and degree_bits in 1 ..= 23")
-    return DeviceBuffer(ctx, size // 8)
+    return table.scratch(ctx, "gl_keccak_sponge_table_scratch_bytes", num_ops, degree_bits,
+                         "gl_keccak_sponge_table_scratch_bytes: num_ops must be at most 2^30 and degree_bits in 1 ..= 23")
 
 
 def _count(ctx, d_ops, num_ops):
     count = ctypes.c_uint64()
     scratch = _scratch(ctx, num_ops, 1)
-    _lib.call("gl_keccak_sponge_table_trace", d_ops.ptr if d_ops is not None else None, num_ops, None, 1, None, 0, scratch.ptr, ctypes.byref(count),
-              ctx.ptr)
+    _lib.call("gl_keccak_sponge_table_trace", table.ptr(d_ops), num_ops, None, 1, None, 0, scratch.ptr, ctypes.byref(count), ctx.ptr)
     return int(count.value)
 
 
@@ -311,19 +293,12 @@ def generate_trace(ctx, ops, data=None, degree_bits=None, trace_stride=None):
     the operations take are left in the buffer's attribute `rows`."""
     if data is None and not isinstance(ops, (DeviceBuffer, np.ndarray)):
         ops, data = ops_to_words(ops)
-    d_ops, num_ops, d_bytes, bytes_ptr = _device_ops(ctx, ops, data)
-    ops_ptr = d_ops.ptr if d_ops is not None else None
+    d_ops, num_ops, d_bytes, bytes_ptr = _device_ops(ctx, ops, data)  # d_bytes: an upload of this call lives until the return
     if degree_bits is None:
         degree_bits = max(1, (max(_count(ctx, d_ops, num_ops), 1) - 1).bit_length())
-    n = 1 << degree_bits
-    stride = n if trace_stride is None else int(trace_stride)
-    scratch = _scratch(ctx, num_ops, degree_bits)
-    d_trace = DeviceBuffer(ctx, NUM_COLUMNS * max(stride, 1))
-    count = ctypes.c_uint64()
-    _lib.call("gl_keccak_sponge_table_trace", ops_ptr, num_ops, bytes_ptr, degree_bits, d_trace.ptr, stride, scratch.ptr, ctypes.byref(count), ctx.ptr)
-    ctx.synchronize()  # the scratch and the uploads of this call are released here: the kernels must have finished with them
-    d_trace.rows = int(count.value)
-    return d_trace
+    # synchronised: the scratch and the uploads of this call are released on return
+    return table.generate_trace(ctx, "gl_keccak_sponge_table_trace", [table.ptr(d_ops), num_ops, bytes_ptr], degree_bits, trace_stride,
+                                NUM_COLUMNS, scratch=_scratch(ctx, num_ops, degree_bits), counted=True)
 
 
 def derive_ops(ctx, d_trace, degree_bits, rows, num_bytes=None, trace_stride=None, keccak=True, logic=True, memory=True):

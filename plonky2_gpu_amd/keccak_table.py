@@ -12,12 +12,7 @@ The bit recompositions (acc.doubles() + bit over 32 bits) run through an ACC acc
 joined by one shift: 32 weights up to 2^31 on one accumulator would break its overflow contract. rc_value_bit(r, i) is known when
 the program is emitted: the sum over the rounds of flag_r * rc_value_bit(r, i) keeps the rounds whose bit is 1 (weight 1) and is
 left out altogether for the 57 bit positions no round constant has — xor_gen(bit, 0) is the bit."""
-import ctypes
-
-import numpy as np
-
-from . import _lib
-from .device import DeviceBuffer
+from . import table
 from .stark import CtlColumn, StarkAsm, StarkDesc
 
 NUM_ROUNDS = 24
@@ -238,32 +233,14 @@ def ctl_filter():
 
 def native_program():
     """gl_keccak_table_program: (instrs, immediates, number of constraints) as the library emits them — program() word for word"""
-    out = _lib.GlGatePrograms()
-    _lib.call("gl_keccak_table_program", ctypes.byref(out))
-    try:
-        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
-        imms = [int(v) for v in np.ctypeslib.as_array(ctypes.cast(out.immediates, ctypes.POINTER(ctypes.c_uint64)), shape=(out.num_immediates,))]
-        if out.gates or out.num_gates:
-            raise RuntimeError("gl_keccak_table_program: a STARK program has no gate descriptors")
-        return instrs, imms, int(out.num_gate_constraints)
-    finally:
-        _lib.load().gl_gate_programs_free(ctypes.byref(out))
+    return table.native_program("gl_keccak_table_program")
 
 
 def generate_trace(ctx, inputs, degree_bits, trace_stride=None):
     """gl_keccak_table_trace: the trace of the Keccak-f[1600] states `inputs` ([num_inputs][25] words, input[5 y + x]; host array or
     DeviceBuffer) with 2^degree_bits rows as a DeviceBuffer [2430][trace_stride] (default 2^degree_bits), built on the context's
     stream; the rows behind the inputs are permutations of the zero state."""
-    n = 1 << degree_bits
-    stride = n if trace_stride is None else int(trace_stride)
-    if isinstance(inputs, DeviceBuffer):
-        d_in, num_inputs = inputs, inputs.n // NUM_INPUTS
-    else:
-        host = np.ascontiguousarray(np.asarray(inputs, dtype=np.uint64).reshape(-1, NUM_INPUTS))
-        num_inputs = host.shape[0]
-        d_in = DeviceBuffer.from_host(ctx, host) if num_inputs else None
-    d_trace = DeviceBuffer(ctx, NUM_COLUMNS * max(stride, 1))
-    _lib.call("gl_keccak_table_trace", d_in.ptr if d_in is not None else None, num_inputs, degree_bits, d_trace.ptr, stride, ctx.ptr)
-    if d_in is not None and d_in is not inputs:
-        ctx.synchronize()  # the upload's buffer is released here: the kernel must have read it
-    return d_trace
+    d_in, num_inputs = table.device_records(ctx, inputs, NUM_INPUTS)
+    uploaded = d_in is not None and d_in is not inputs  # the upload's buffer is released on return: the kernel must have read it
+    return table.generate_trace(ctx, "gl_keccak_table_trace", [table.ptr(d_in), num_inputs], degree_bits, trace_stride, NUM_COLUMNS,
+                                synchronize=uploaded)

@@ -13,11 +13,9 @@ table's AND / OR / XOR and the Keccak sponge's byte XORs look into it.
 The 32-bit recompositions and the weighted sum of the 32 bit products run through an ACC accumulator in two blocks of 16 weights
 2^0 .. 2^15 joined by one shift, as the Keccak-f table's do: 32 weights up to 2^31 on one accumulator would break its overflow
 contract."""
-import ctypes
-
 import numpy as np
 
-from . import _lib
+from . import _lib, table
 from .device import DeviceBuffer
 from .keccak_table import _limb
 from .stark import CtlColumn, StarkAsm, StarkDesc
@@ -102,16 +100,7 @@ def ctl_filter():
 
 def native_program():
     """gl_logic_table_program: (instrs, immediates, number of constraints) as the library emits them — program() word for word"""
-    out = _lib.GlGatePrograms()
-    _lib.call("gl_logic_table_program", ctypes.byref(out))
-    try:
-        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
-        imms = [int(v) for v in np.ctypeslib.as_array(ctypes.cast(out.immediates, ctypes.POINTER(ctypes.c_uint64)), shape=(out.num_immediates,))]
-        if out.gates or out.num_gates:
-            raise RuntimeError("gl_logic_table_program: a STARK program has no gate descriptors")
-        return instrs, imms, int(out.num_gate_constraints)
-    finally:
-        _lib.load().gl_gate_programs_free(ctypes.byref(out))
+    return table.native_program("gl_logic_table_program")
 
 
 # ---------------------------------------------------------------- the trace
@@ -138,19 +127,10 @@ def generate_trace(ctx, ops, degree_bits=None, trace_stride=None):
     2^degree_bits rows as a DeviceBuffer [523][trace_stride] (default 2^degree_bits), built on the context's stream: the list order
     is the row order, the rows behind the operations are zero. degree_bits=None takes the smallest trace that holds them, the
     reference's."""
-    if isinstance(ops, DeviceBuffer):
-        d_ops, num_ops = ops, ops.n // OP_WORDS
-    else:
-        host = np.ascontiguousarray(np.asarray(ops, dtype=np.uint64).reshape(-1, OP_WORDS))
-        num_ops = host.shape[0]
-        d_ops = DeviceBuffer.from_host(ctx, host) if num_ops else None
+    d_ops, num_ops = table.device_records(ctx, ops, OP_WORDS)
     if degree_bits is None:
         degree_bits = max(1, (max(num_ops, 1) - 1).bit_length())
-    n = 1 << degree_bits
-    stride = n if trace_stride is None else int(trace_stride)
     scratch = DeviceBuffer(ctx, _lib.GL_LOGIC_TABLE_SCRATCH_BYTES // 8)
-    d_trace = DeviceBuffer(ctx, NUM_COLUMNS * max(stride, 1))
-    _lib.call("gl_logic_table_trace", d_ops.ptr if d_ops is not None else None, num_ops, degree_bits, d_trace.ptr, stride, scratch.ptr, ctx.ptr)
-    if d_ops is not None and d_ops is not ops:
-        ctx.synchronize()  # the upload's buffer is released here: the kernel must have read it
-    return d_trace
+    uploaded = d_ops is not None and d_ops is not ops  # the upload's buffer is released on return: the kernel must have read it
+    return table.generate_trace(ctx, "gl_logic_table_trace", [table.ptr(d_ops), num_ops], degree_bits, trace_stride, NUM_COLUMNS,
+                                scratch=scratch, synchronize=uploaded)

@@ -13,8 +13,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
-from .device import DeviceBuffer
+from . import _lib, table
 from .stark import CtlColumn, StarkAsm, StarkDesc
 
 NUM_CHANNELS = 6
@@ -138,16 +137,7 @@ def ctl_filter():
 
 def native_program():
     """gl_memory_table_program: (instrs, immediates, number of constraints) as the library emits them — program() word for word"""
-    out = _lib.GlGatePrograms()
-    _lib.call("gl_memory_table_program", ctypes.byref(out))
-    try:
-        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
-        imms = [int(v) for v in np.ctypeslib.as_array(ctypes.cast(out.immediates, ctypes.POINTER(ctypes.c_uint64)), shape=(out.num_immediates,))]
-        if out.gates or out.num_gates:
-            raise RuntimeError("gl_memory_table_program: a STARK program has no gate descriptors")
-        return instrs, imms, int(out.num_gate_constraints)
-    finally:
-        _lib.load().gl_gate_programs_free(ctypes.byref(out))
+    return table.native_program("gl_memory_table_program")
 
 
 # ---------------------------------------------------------------- the trace
@@ -165,19 +155,12 @@ def ops_to_words(ops):
 
 def _device_ops(ctx, ops):
     """(DeviceBuffer, number of operations)"""
-    if isinstance(ops, DeviceBuffer):
-        return ops, ops.n // OP_WORDS
-    host = np.ascontiguousarray(np.asarray(ops, dtype=np.uint64).reshape(-1, OP_WORDS))
-    if host.shape[0] < 2:
-        raise ValueError("the memory table takes at least two operations")
-    return DeviceBuffer.from_host(ctx, host), host.shape[0]
+    return table.device_records(ctx, ops, OP_WORDS, min_ops=2, too_few="the memory table takes at least two operations")
 
 
 def _scratch(ctx, num_ops, degree_bits):
-    size = _lib.load().gl_memory_table_scratch_bytes(num_ops, degree_bits)
-    if not size:
-        raise ValueError("gl_memory_table_scratch_bytes: num_ops must be in 2 ..= 2^30 and degree_bits in 1 ..= 23")
-    return DeviceBuffer(ctx, size // 8)
+    return table.scratch(ctx, "gl_memory_table_scratch_bytes", num_ops, degree_bits,
+                         "gl_memory_table_scratch_bytes: num_ops must be in 2 ..= 2^30 and degree_bits in 1 ..= 23")
 
 
 def _count(ctx, d_ops, num_ops):
@@ -202,12 +185,7 @@ def generate_trace(ctx, ops, degree_bits=None, trace_stride=None):
     d_ops, num_ops = _device_ops(ctx, ops)
     if degree_bits is None:
         degree_bits = max(1, (_count(ctx, d_ops, num_ops) - 1).bit_length())
-    n = 1 << degree_bits
-    stride = n if trace_stride is None else int(trace_stride)
-    scratch = _scratch(ctx, num_ops, degree_bits)
-    d_trace = DeviceBuffer(ctx, NUM_COLUMNS * max(stride, 1))
-    count = ctypes.c_uint64()
-    _lib.call("gl_memory_table_trace", d_ops.ptr, num_ops, degree_bits, d_trace.ptr, stride, scratch.ptr, ctypes.byref(count), ctx.ptr)
-    ctx.synchronize()  # the scratch and an upload of this call are released here: the kernels must have finished with them
-    d_trace.rows = int(count.value)
-    return d_trace
+    # synchronised: the scratch and an upload of this call are released on return
+    return table.generate_trace(ctx, "gl_memory_table_trace", [d_ops.ptr, num_ops], degree_bits, trace_stride, NUM_COLUMNS,
+                                scratch=_scratch(ctx, num_ops, degree_bits), counted=True)
+

@@ -25,6 +25,7 @@ from . import _lib
 from .device import DeviceBuffer
 from .gate_program import ACC, ACCR, ADD, EMIT, LOAD_CONST, LOAD_IMM, LOAD_PI, LOAD_WIRE, MUL, MULK, SUB, GateAsm, ImmediatePool  # noqa: F401
 from .serialization import Buffer
+from .table import call_programs
 
 LOAD_NEXT, EMIT_TRANSITION, EMIT_FIRST_ROW, EMIT_LAST_ROW = 11, 12, 13, 14
 EMITS = (EMIT, EMIT_TRANSITION, EMIT_FIRST_ROW, EMIT_LAST_ROW)
@@ -596,14 +597,8 @@ def split_program(desc, unit_instrs):
     (instrs [k][4] uint16, (first, one past the last) of the program's EMITs the unit yields). Every unit is a program of its own
     over desc.immediates; a value that lives across a cut is computed again in each unit that reads it. Needs no device."""
     d, _keep = _c_stark_desc(desc)
-    out = _lib.GlGatePrograms()
-    _lib.call("gl_stark_split_program", ctypes.byref(d), int(unit_instrs), ctypes.byref(out))
-    try:
-        instrs = np.ctypeslib.as_array(ctypes.cast(out.instrs, ctypes.POINTER(ctypes.c_uint16)), shape=(out.num_instrs, 4)).copy()
-        gates = np.ctypeslib.as_array(ctypes.cast(out.gates, ctypes.POINTER(ctypes.c_uint32)), shape=(out.num_gates, 6)).copy()
-        return [(instrs[int(g[4]):int(g[4]) + int(g[5])], (int(g[2]), int(g[3]))) for g in gates]
-    finally:
-        _lib.load().gl_gate_programs_free(ctypes.byref(out))
+    instrs, gates, _, _ = call_programs("gl_stark_split_program", ctypes.byref(d), int(unit_instrs))
+    return [(instrs[int(g[4]):int(g[4]) + int(g[5])], (int(g[2]), int(g[3]))) for g in gates]
 
 
 # ---------------------------------------------------------------- wire format (include/plonky2_hip.h, gl_stark_tables_prove)

@@ -1,4 +1,6 @@
 """Shared helpers for the -m gpu parity tests (HIP path through the C ABI vs the CPU oracle)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -15,6 +17,20 @@ def gpu():
     ctx = pg.Context(0)
     yield ctx
     ctx.close()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def kernel_cache(request, tmp_path_factory):
+    """An empty kernel cache of its own for every module that imports this fixture (the library reads the variable at every
+    compile); the variable is put back behind the module."""
+    cache = str(tmp_path_factory.mktemp(request.module.__name__ + "_kernel_cache"))
+    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
+    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
+    yield cache
+    if saved is None:
+        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
+    else:
+        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 def bitrev_perm(log_n):

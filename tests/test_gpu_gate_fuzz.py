@@ -27,24 +27,11 @@ import gate_fuzz as gf  # noqa: E402
 import gate_fuzz_device as gd  # noqa: E402
 import gate_fuzz_variant_child as child  # noqa: E402
 import test_gate_fuzz as tgf  # noqa: E402  (MUTANTS, ACCEPTED: the programs the restated rules refuse and accept)
-from gpu_util import gpu  # noqa: E402,F401
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 
 P = gf.P
 LIFTED = gf.LIFTED_A + [gf.FAMILY_B[j] for j in gf.LIFTED_B]
 GENERATED = {}  # case -> gd.generated(...) of the product library's kernel, filled as the cases run
-
-
-@pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile"""
-    cache = str(tmp_path_factory.mktemp("gate_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 def _check_case(gpu, i, lifted=False):

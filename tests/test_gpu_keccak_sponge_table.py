@@ -18,36 +18,22 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import ctl_ref as cr  # noqa: E402
-import generic_prove_ref as gr  # noqa: E402
 import keccak_sponge_table_instances as ki  # noqa: E402
 import keccak_sponge_table_ref as kr  # noqa: E402
 import keccak_table_ref  # noqa: E402
 import logic_table_ref  # noqa: E402
 import memory_table_ref  # noqa: E402
 import stark_instances as si  # noqa: E402
-import stark_ref as sr  # noqa: E402
-from gpu_util import gpu  # noqa: E402,F401
+import table_harness as th  # noqa: E402
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 from strided import Strided, filler  # noqa: E402
 
 ONES = (1 << 64) - 1
-HASHERS = {"poseidon": gr.PoseidonHasher(), "keccak": gr.KeccakHasher()}
+HASHERS = th.HASHERS
 COLUMNS = 414
 LISTS = {"mixed": ki.mixed, "system": ki.system_ops, "none": lambda: [], "many1": lambda: ki.many(1), "many3": lambda: ki.many(3),
          "many34": lambda: ki.many(34), "many64": lambda: ki.many(64), "many300": lambda: ki.many(300)}
 LISTS.update({"single%d" % length: (lambda length=length: ki.single(length)) for length in ki.LENGTHS})
-
-
-@pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile"""
-    cache = str(tmp_path_factory.mktemp("keccak_sponge_table_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 # ---------------------------------------------------------------- instances and reference traces
@@ -75,11 +61,6 @@ def _reference(name, degree_bits):
     assert cols.shape == (COLUMNS, 1 << degree_bits)
     cols.setflags(write=False)
     return cols
-
-
-def _first_difference(got, exp):
-    bad = np.argwhere(got != exp)
-    return None if bad.size == 0 else ("first (column, row) that differs", bad[0].tolist(), len(bad), hex(int(got[tuple(bad[0])])), hex(int(exp[tuple(bad[0])])))
 
 
 def _scratch(gpu, num_ops, degree_bits):
@@ -136,7 +117,7 @@ def test_one_operation_of_every_length(gpu, length):
     name = "single%d" % length
     bits = _exact_bits(name)
     assert 1 << bits == max(2, kr.next_power_of_two(length // 136 + 1))
-    assert _first_difference(_run(gpu, name, bits, byte_offset=length % 8), _reference(name, bits)) is None
+    assert th.first_difference(_run(gpu, name, bits, byte_offset=length % 8), _reference(name, bits)) is None
 
 
 @pytest.mark.gpu
@@ -150,13 +131,13 @@ def test_trace_equals_generate_trace_rows(gpu, name, extra_bits, pad):
     if extra_bits:
         half = 1 << (bits - 1)
         assert (exp[:, :half] == _reference(name, bits - 1)).all() and not exp[:, half:].any()
-    assert _first_difference(_run(gpu, name, bits, pad), exp) is None
+    assert th.first_difference(_run(gpu, name, bits, pad), exp) is None
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("byte_offset", [1, 3, 7])
 def test_bytes_at_an_odd_address(gpu, byte_offset):
-    assert _first_difference(_run(gpu, "mixed", 5, byte_offset=byte_offset), _reference("mixed", 5)) is None
+    assert th.first_difference(_run(gpu, "mixed", 5, byte_offset=byte_offset), _reference("mixed", 5)) is None
 
 
 @pytest.mark.gpu
@@ -166,11 +147,11 @@ def test_generate_trace_rows_and_derive_ops_of_the_module(gpu):
 
     ops = [(o.context, o.segment, o.virt, o.timestamp, o.input) for o in _ops("mixed")]
     d = ks.generate_trace(gpu, ops)  # the count first, then the smallest trace
-    assert d.rows == 22 and _first_difference(d.download().reshape(COLUMNS, 32), _reference("mixed", 5)) is None
+    assert d.rows == 22 and th.first_difference(d.download().reshape(COLUMNS, 32), _reference("mixed", 5)) is None
     words, data = ks.ops_to_words(ops)
     assert ks.rows(gpu, words) == 22 == ks.rows(gpu, pg.DeviceBuffer.from_host(gpu, words))
     d = ks.generate_trace(gpu, pg.DeviceBuffer.from_host(gpu, words), data, degree_bits=6, trace_stride=64 + 24)
-    assert _first_difference(d.download().reshape(COLUMNS, 88)[:, :64], _reference("mixed", 6)) is None
+    assert th.first_difference(d.download().reshape(COLUMNS, 88)[:, :64], _reference("mixed", 6)) is None
     empty = ks.generate_trace(gpu, [])
     assert empty.rows == 0 and empty.n == 2 * COLUMNS and not empty.download().any()
     keccak, logic, memory = ks.derive_ops(gpu, d, 6, 22, trace_stride=88)  # the byte count read back from the trace
@@ -245,7 +226,7 @@ def test_data_refusals_write_nothing_and_name_the_lowest_record(gpu):
     d_ops = pg.DeviceBuffer.from_host(gpu, words)
     rows, err = _call(gpu, d_ops.ptr, num_ops, bytes_ptr, 5, trace.ptr, n, scratch.ptr)
     assert err is None and rows == 22
-    assert _first_difference(trace.download().reshape(COLUMNS, n), _reference("mixed", 5)) is None
+    assert th.first_difference(trace.download().reshape(COLUMNS, n), _reference("mixed", 5)) is None
     del d_bytes
 
 
@@ -345,7 +326,7 @@ def test_derived_lists_equal_keccak_sponge_log(gpu, name, pad, which):
     for k, (g, e) in enumerate(zip(got, exp)):
         assert (g is None) == (k not in which)
         if g is not None:
-            assert _first_difference(g, e) is None, k
+            assert th.first_difference(g, e) is None, k
     assert (d_trace.download() == before).all()
 
 
@@ -396,43 +377,21 @@ def test_the_derived_lists_build_the_other_three_tables(gpu):
 
     traces = _device_traces(gpu)
     keccak_inputs, logic_ops, memory_ops = _log("system")
-    assert traces[ki.SPONGE].rows == 5 and _first_difference(traces[ki.SPONGE].download().reshape(COLUMNS, 8), _reference("system", 3)) is None
-    assert _first_difference(traces[ki.KECCAK].download().reshape(kt.NUM_COLUMNS, 128), keccak_table_ref.generate_trace_rows(keccak_inputs, 128).T) is None
-    assert _first_difference(traces[ki.LOGIC].download().reshape(lt.NUM_COLUMNS, 32), logic_table_ref.trace_of_words(logic_ops, 5)) is None
+    assert traces[ki.SPONGE].rows == 5 and th.first_difference(traces[ki.SPONGE].download().reshape(COLUMNS, 8), _reference("system", 3)) is None
+    assert th.first_difference(traces[ki.KECCAK].download().reshape(kt.NUM_COLUMNS, 128), keccak_table_ref.generate_trace_rows(keccak_inputs, 128).T) is None
+    assert th.first_difference(traces[ki.LOGIC].download().reshape(lt.NUM_COLUMNS, 32), logic_table_ref.trace_of_words(logic_ops, 5)) is None
     exp, rows = memory_table_ref.trace_of_words(memory_ops)
     assert traces[ki.MEMORY].rows == rows == 440 and exp.shape == (mt.NUM_COLUMNS, 512)
-    assert _first_difference(traces[ki.MEMORY].download().reshape(mt.NUM_COLUMNS, 512), exp) is None
+    assert th.first_difference(traces[ki.MEMORY].download().reshape(mt.NUM_COLUMNS, 512), exp) is None
     assert ks.NUM_COLUMNS == COLUMNS
 
 
 # ---------------------------------------------------------------- single proofs
-FP = si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,))
 PROVABLE = {8: "system", 64: "many34"}  # 5 rows in 8; 63 in 64
-
-
-@functools.lru_cache(maxsize=None)
-def _stark():
-    from plonky2_gpu_amd import keccak_sponge_table as ks
-
-    instrs, immediates = ks.program()
-    return kr.KeccakSpongeTableStark(instrs, immediates)
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_proof(hasher, num_challenges, n):
-    from oracle import accel
-
-    cols = _reference(PROVABLE[n], n.bit_length() - 1)
-    trace = [[int(v) for v in col] for col in cols]
-    with accel.c_backend():
-        return sr.proof_bytes(HASHERS[hasher], sr.prove(HASHERS[hasher], _stark(), num_challenges, FP, trace, []))
-
-
-def _device_trace(ctx, n):
-    from plonky2_gpu_amd import keccak_sponge_table as ks
-
-    words, data = _words(PROVABLE[n])
-    return ks.generate_trace(ctx, words, data, degree_bits=n.bit_length() - 1)
+TABLE = th.Table("keccak_sponge_table", kr.KeccakSpongeTableStark, COLUMNS, (8, 64), reference_trace=lambda n: _reference(PROVABLE[n], n.bit_length() - 1),
+                 device_trace=lambda ctx, n: TABLE.module.generate_trace(ctx, *_words(PROVABLE[n]), degree_bits=n.bit_length() - 1),
+                 flip=lambda ks: (ks.UPDATED_STATE_U32S + 11, 2))
+_stark = TABLE.stark
 
 
 @pytest.mark.gpu
@@ -442,26 +401,8 @@ def _device_trace(ctx, n):
 def test_proof_bytes_of_the_device_built_trace_equal_the_reference(gpu, hasher, num_challenges, compiled, n):
     """interpreted and compiled, with both hashers (Keccak with 2 challenges would have quotient leaves of 4 elements, which
     KeccakHash<25> cannot hash: 1 there); the reference's verifier accepts"""
-    import plonky2_gpu_amd as pg
-    from oracle import accel
-    from plonky2_gpu_amd import keccak_sponge_table as ks
-    from plonky2_gpu_amd import stark as pstark
-
     assert kr.rows_needed(_ops(PROVABLE[n])) == {8: 5, 64: 63}[n]
-    exp = _reference_proof(hasher, num_challenges, n)
-    ns = pg.NativeStark(gpu, ks.stark_desc(n.bit_length() - 1, num_challenges, FP), hasher, compiled=compiled, unit_instrs=0 if compiled else None)
-    try:
-        assert bool(ns.is_compiled) == compiled
-        d_trace = _device_trace(gpu, n)
-        data = ns.prove_bytes(d_trace, [])
-        assert data == exp
-        assert ns.prove_bytes(d_trace, []) == exp  # on recycled buffers
-    finally:
-        ns.close()
-    parsed = pstark.proof_from_bytes(data, ns.desc, hasher)
-    assert pstark.proof_to_bytes(parsed, ns.desc, hasher) == data
-    with accel.c_backend():
-        assert sr.verify(HASHERS[hasher], _stark(), num_challenges, FP, parsed, evaluator="closure" if compiled else "program")
+    th.check_proof_bytes(TABLE, gpu, hasher, num_challenges, n, compiled=compiled, verify="closure" if compiled else "program")
 
 
 @pytest.mark.gpu
@@ -469,24 +410,9 @@ def test_a_flipped_cell_of_updated_state_on_a_full_block_row_is_rejected(gpu):
     """row 2 of the system's trace is the first full-block row of the 300-byte operation: its updated_state_u32s is the next row's
     original state (constraint family 7). The device proves the violated trace as the reference does, and the verifier
     (tests/stark_verify.py, which accepts the proof of the untouched trace) rejects at zeta."""
-    import plonky2_gpu_amd as pg
-    import stark_verify
-    from plonky2_gpu_amd import keccak_sponge_table as ks
-
-    ns = pg.NativeStark(gpu, ks.stark_desc(3, 2, FP))
-    try:
-        d_trace = _device_trace(gpu, 8)
-        assert stark_verify.accepts(ns.desc, ns.prove_bytes(d_trace, []))
-        column, row = ks.UPDATED_STATE_U32S + 11, 2
-        assert _reference("system", 3)[ks.IS_FULL_INPUT_BLOCK, row] == 1
-        cell = d_trace.download(column * 8 + row, 1)
-        assert cell[0] == _reference("system", 3)[column, row]
-        d_trace.upload(cell ^ np.uint64(1), column * 8 + row)
-        data = ns.prove_bytes(d_trace, [])
-    finally:
-        ns.close()
-    with pytest.raises(AssertionError, match="Mismatch between evaluation and opening"):
-        stark_verify.accepts(ns.desc, data)
+    column, row = TABLE.flip(TABLE.module)
+    assert _reference("system", 3)[TABLE.module.IS_FULL_INPUT_BLOCK, row] == 1
+    th.check_flipped_cell_is_rejected(TABLE, gpu, "stark_verify")
 
 
 # ---------------------------------------------------------------- the system

@@ -5,7 +5,6 @@ trees and transforms in C); the algebra of the STARK stays Python."""
 import functools
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -13,17 +12,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import ctl_ref as cr  # noqa: E402
-import generic_prove_ref as gr  # noqa: E402
 import keccak_ref  # noqa: E402
 import keccak_table_ref as kr  # noqa: E402
 import stark_instances as si  # noqa: E402
-import stark_ref as sr  # noqa: E402
+import table_harness as th  # noqa: E402
 from gpu_util import gpu  # noqa: E402,F401
 from strided import Strided  # noqa: E402
 
 P = 0xFFFFFFFF00000001
 ONES = (1 << 64) - 1
-HASHERS = {"poseidon": gr.PoseidonHasher(), "keccak": gr.KeccakHasher()}
+HASHERS = th.HASHERS
 COLUMNS = 2430
 
 
@@ -134,24 +132,10 @@ def test_trace_refusals_write_nothing(gpu):
 
 
 # ---------------------------------------------------------------- proofs of the 32-row trace
-FP = si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,))
-
-
-@functools.lru_cache(maxsize=None)
-def _stark():
-    from plonky2_gpu_amd import keccak_table as kt
-
-    instrs, immediates = kt.program()
-    return kr.KeccakTableStark(instrs, immediates)
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_proof(hasher, num_challenges):
-    from oracle import accel
-
-    trace = [[int(v) for v in col] for col in _reference_trace(1, 32)]
-    with accel.c_backend():
-        return sr.proof_bytes(HASHERS[hasher], sr.prove(HASHERS[hasher], _stark(), num_challenges, FP, trace, []))
+TABLE = th.Table("keccak_table", kr.KeccakTableStark, COLUMNS, (32,), reference_trace=lambda n: _reference_trace(1, n),
+                 device_trace=lambda ctx, n: TABLE.module.generate_trace(ctx, _pool()[:1], n.bit_length() - 1),
+                 flip=lambda kt: (kt.reg_a_prime(2, 3, 40), 7))
+_stark = TABLE.stark
 
 
 @pytest.mark.gpu
@@ -159,68 +143,26 @@ def _reference_proof(hasher, num_challenges):
 def test_proof_bytes_of_the_device_built_trace_equal_the_reference(gpu, hasher, num_challenges):
     """2430 columns and a program of 47 000 instructions through every stage of gl_stark_prove. Keccak with 2 challenges would have
     quotient leaves of 4 elements, which KeccakHash<25> cannot hash (the reference panics): 1 and 3 there."""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import keccak_table as kt
-    from plonky2_gpu_amd import stark as pstark
-
-    exp = _reference_proof(hasher, num_challenges)
-    ns = pg.NativeStark(gpu, kt.stark_desc(5, num_challenges, FP), hasher)
-    try:
-        d_trace = kt.generate_trace(gpu, _pool()[:1], 5)
-        data = ns.prove_bytes(d_trace, [])
-        assert data == exp
-        assert ns.prove_bytes(d_trace, []) == exp  # on recycled buffers
-    finally:
-        ns.close()
-    parsed = pstark.proof_from_bytes(data, ns.desc, hasher)
-    assert pstark.proof_to_bytes(parsed, ns.desc, hasher) == data
+    th.check_proof_bytes(TABLE, gpu, hasher, num_challenges, 32)
 
 
 @pytest.mark.gpu
 def test_quotient_polys_on_random_words_equal_the_reference(gpu):
     """the 47 000-instruction program through the interpreter at 2430 columns, 2^5 rows, on uniformly random words in place of the
     LDEs (every constraint non-zero), at the tight and at a padded column pitch"""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import keccak_table as kt
-
     rng = np.random.default_rng(55)
     lde = rng.integers(0, P, size=(COLUMNS, 64), dtype=np.uint64)
     alphas = [int(x) for x in rng.integers(0, P, size=2, dtype=np.uint64)]
-    exp = np.array(sr.compute_quotient_polys(_stark(), 2, 5, 1, [[int(v) for v in row] for row in lde.T], None, None, [], alphas), dtype=np.uint64)
-    assert exp.shape == (2, 64) and exp.all()
-    ns = pg.NativeStark(gpu, kt.stark_desc(5, 2, FP))
-    try:
-        for stride in (64, 64 + 6):
-            t = Strided(gpu, lde, stride)
-            got = ns.quotient_polys(t.ptr, None, stride, alphas, None, [])
-            assert (t.polys() == lde).all()
-            t.free()
-            bad = np.argwhere(got != exp)
-            assert bad.size == 0, ("column pitch", stride, "first (challenge, coefficient) that differs", bad[0].tolist(), len(bad))
-    finally:
-        ns.close()
+    th.check_quotient_polys(TABLE, gpu, lde, alphas)
 
 
 @pytest.mark.gpu
 def test_a_flipped_a_prime_bit_gives_a_proof_the_verifier_rejects(gpu):
     """quotient_degree_factor 2 is a power of two: the reference's trim cannot fail, its prover returns a proof of the violated trace,
     and verification fails at zeta. The device does the same."""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import keccak_table as kt
-    from plonky2_gpu_amd import stark as pstark
-
-    ns = pg.NativeStark(gpu, kt.stark_desc(5, 2, FP))
-    try:
-        d_trace = kt.generate_trace(gpu, _pool()[:1], 5)
-        column, row = kt.reg_a_prime(2, 3, 40), 7
-        cell = d_trace.download(column * 32 + row, 1)
-        assert cell[0] in (0, 1) and cell[0] == _reference_trace(1, 32)[column, row]
-        d_trace.upload(cell ^ np.uint64(1), column * 32 + row)
-        parsed = pstark.proof_from_bytes(ns.prove_bytes(d_trace, []), ns.desc)
-    finally:
-        ns.close()
-    with pytest.raises(AssertionError, match="Mismatch between evaluation and opening"):
-        sr.verify(HASHERS["poseidon"], _stark(), 2, FP, parsed)
+    column, row = TABLE.flip(TABLE.module)
+    assert _reference_trace(1, 32)[column, row] in (0, 1)
+    th.check_flipped_cell_is_rejected(TABLE, gpu, "stark_ref")
 
 
 # ---------------------------------------------------------------- two tables and the cross-table lookup
@@ -240,11 +182,6 @@ class _Sponge:
     @staticmethod
     def closure(F, local, nxt, pis, consumer):
         consumer.constraint(F.mul(local[100], F.sub(local[100], F.one)))
-
-
-class _System:
-    def __init__(self, tables, lookups):
-        self.tables, self.lookups, self.ctl_closures = tables, lookups, None
 
 
 @pytest.mark.gpu
@@ -273,7 +210,7 @@ def test_two_tables_with_the_keccak_lookup_equal_the_reference(gpu):
     lookups = [CrossTableLookup([TableWithColumns(0, [CtlColumn.single(c) for c in range(100)], CtlColumn.single(100))],
                                 TableWithColumns(1, kt.ctl_data(), kt.ctl_filter()))]
     fps = [si.fri_params(rate_bits=1, cap_height=1, arity_bits=ab, num_query_rounds=4, proof_of_work_bits=2) for ab in ((), (2,))]
-    system = _System([sponge, _stark()], lookups)
+    system = th.System([sponge, _stark()], lookups)
     keccak_trace = [[int(v) for v in col] for col in _reference_trace(2, 64)]
     with accel.c_backend():
         exp = cr.proofs_bytes(HASHERS["poseidon"], cr.prove_tables(HASHERS["poseidon"], system, 1, fps, [sponge_trace, keccak_trace]))
@@ -292,31 +229,4 @@ def test_two_tables_with_the_keccak_lookup_equal_the_reference(gpu):
 # ---------------------------------------------------------------- two contexts, two threads
 @pytest.mark.gpu
 def test_two_contexts_on_two_threads_build_and_prove(gpu):
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import keccak_table as kt
-
-    exp = _reference_proof("poseidon", 2)
-    ns = pg.NativeStark(gpu, kt.stark_desc(5, 2, FP))
-    other = pg.Context(0)
-    try:
-        alone = ns.prove_bytes(kt.generate_trace(gpu, _pool()[:1], 5), [])
-        assert alone == exp
-        got, errors = [None, None], []
-
-        def work(k, ctx):
-            try:
-                for _ in range(2):
-                    got[k] = ns.prove_bytes(kt.generate_trace(ctx, _pool()[:1], 5), [], ctx=ctx)
-            except Exception as e:  # noqa: BLE001
-                errors.append(e)
-
-        threads = [threading.Thread(target=work, args=(k, ctx)) for k, ctx in enumerate((gpu, other))]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        assert not errors, errors
-        assert got == [alone, alone]
-    finally:
-        ns.close()
-        other.close()
+    th.check_two_contexts_on_two_threads(TABLE, gpu)

@@ -9,7 +9,6 @@ even padded pitch and at an odd one, which the 16-byte store path of the measure
 import functools
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -17,31 +16,18 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import ctl_ref as cr  # noqa: E402
-import generic_prove_ref as gr  # noqa: E402
 import logic_table_instances as li  # noqa: E402
 import logic_table_ref as lr  # noqa: E402
 import stark_instances as si  # noqa: E402
 import stark_ref as sr  # noqa: E402
-from gpu_util import gpu  # noqa: E402,F401
+import table_harness as th  # noqa: E402
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 from strided import Strided, filler  # noqa: E402
 
 P = 0xFFFFFFFF00000001
 ONES = (1 << 64) - 1
-HASHERS = {"poseidon": gr.PoseidonHasher(), "keccak": gr.KeccakHasher()}
+HASHERS = th.HASHERS
 COLUMNS = 523
-
-
-@pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile"""
-    cache = str(tmp_path_factory.mktemp("logic_table_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 # ---------------------------------------------------------------- instances and reference traces
@@ -74,11 +60,6 @@ def _call(gpu, d_ops, num_ops, degree_bits, d_trace, stride, d_scratch):
     return None
 
 
-def _first_difference(got, exp):
-    bad = np.argwhere(got != exp)
-    return None if bad.size == 0 else ("first (column, row) that differs", bad[0].tolist(), len(bad), hex(int(got[tuple(bad[0])])), hex(int(exp[tuple(bad[0])])))
-
-
 SHAPES = [(0, 1), (1, 1), (2, 1), (3, 2), (31, 5), (32, 5), (255, 8), (257, 9), (2049, 12)]
 
 
@@ -101,7 +82,7 @@ def test_trace_equals_generate_trace_rows(gpu, num_ops, degree_bits, pad):
     buf.free()
     if d_ops:
         assert (d_ops.download().reshape(num_ops, 17) == _ops(num_ops)).all()
-    assert _first_difference(got, exp) is None
+    assert th.first_difference(got, exp) is None
 
 
 @pytest.mark.gpu
@@ -122,7 +103,7 @@ def test_trace_one_word_off_a_16_byte_boundary(gpu, num_ops, degree_bits):
     assert (out[:front] == fill[:front]).all() and (out[-tail:] == fill[-tail:]).all()
     body, pads = out[front:-tail].reshape(COLUMNS, stride), fill[front:-tail].reshape(COLUMNS, stride)
     assert (body[:, n:] == pads[:, n:]).all()
-    assert _first_difference(body[:, :n], exp) is None
+    assert th.first_difference(body[:, :n], exp) is None
 
 
 @pytest.mark.gpu
@@ -133,7 +114,7 @@ def test_degree_bits_one_above_the_need_plays_min_rows(gpu, num_ops, degree_bits
     exp = _reference(num_ops, degree_bits)
     assert (exp[:, : 1 << (degree_bits - 1)] == _reference(num_ops, degree_bits - 1)).all() and not exp[:, 1 << (degree_bits - 1) :].any()
     got = lt.generate_trace(gpu, _ops(num_ops), degree_bits=degree_bits).download().reshape(COLUMNS, 1 << degree_bits)
-    assert _first_difference(got, exp) is None
+    assert th.first_difference(got, exp) is None
 
 
 @pytest.mark.gpu
@@ -145,10 +126,10 @@ def test_generate_trace_of_the_module_on_every_family(gpu, family):
     from plonky2_gpu_amd import logic_table as lt
 
     w, exp = _ops(65, family), _reference(65, 7, family)
-    assert _first_difference(lt.generate_trace(gpu, w).download().reshape(COLUMNS, 128), exp) is None
+    assert th.first_difference(lt.generate_trace(gpu, w).download().reshape(COLUMNS, 128), exp) is None
     d_ops = pg.DeviceBuffer.from_host(gpu, w)
     got = lt.generate_trace(gpu, d_ops, trace_stride=128 + 24).download().reshape(COLUMNS, 152)[:, :128]
-    assert _first_difference(got, exp) is None
+    assert th.first_difference(got, exp) is None
     assert not lt.generate_trace(gpu, lt.ops_to_words([])).download().any()
 
 
@@ -171,7 +152,7 @@ def test_both_store_widths_write_the_same_trace(gpu, num_ops, degree_bits):
             _lib.call("gl_debug_logic_table_fill", ops_ptr, num_ops, degree_bits, buf.ptr, n + pad, width, gpu.ptr)
             got = buf.polys((num_ops, degree_bits, pad, width))
             buf.free()
-            assert _first_difference(got, exp) is None, width
+            assert th.first_difference(got, exp) is None, width
     buf = pg.DeviceBuffer(gpu, COLUMNS * (n + 25) + 1)
     for ptr, stride, width, why in ((buf.ptr, n + 25, 2, "even trace_stride"), (buf.at(1), n + 24, 2, "16-byte aligned"), (buf.ptr, n, 3, "rows_per_thread"),
                                     (buf.ptr, n, 0, "rows_per_thread"), (buf.ptr, n - 1, 1, "trace_stride")):
@@ -218,7 +199,7 @@ def test_data_refusals_write_nothing_and_name_the_lowest_record(gpu):
     # ... and the same buffers take the untouched list
     d_ops = pg.DeviceBuffer.from_host(gpu, _ops(num_ops))
     assert _call(gpu, d_ops.ptr, num_ops, 9, trace.ptr, n, scratch.ptr) is None
-    assert _first_difference(trace.download().reshape(COLUMNS, n), _reference(num_ops, 9)) is None
+    assert th.first_difference(trace.download().reshape(COLUMNS, n), _reference(num_ops, 9)) is None
 
 
 @pytest.mark.gpu
@@ -267,32 +248,12 @@ def test_argument_refusals_launch_nothing(gpu):
 
 
 # ---------------------------------------------------------------- proofs
-FP = si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,))
+FP = th.FP
 PROVABLE = {32: 21, 64: 64}  # 11 padding rows in 32; none in 64
-
-
-@functools.lru_cache(maxsize=None)
-def _stark():
-    from plonky2_gpu_amd import logic_table as lt
-
-    instrs, immediates = lt.program()
-    return lr.LogicTableStark(instrs, immediates)
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_proof(hasher, num_challenges, n):
-    from oracle import accel
-
-    cols = _reference(PROVABLE[n], n.bit_length() - 1)
-    trace = [[int(v) for v in col] for col in cols]
-    with accel.c_backend():
-        return sr.proof_bytes(HASHERS[hasher], sr.prove(HASHERS[hasher], _stark(), num_challenges, FP, trace, []))
-
-
-def _device_trace(ctx, n):
-    from plonky2_gpu_amd import logic_table as lt
-
-    return lt.generate_trace(ctx, _ops(PROVABLE[n]), degree_bits=n.bit_length() - 1)
+TABLE = th.Table("logic_table", lr.LogicTableStark, COLUMNS, (32, 64), reference_trace=lambda n: _reference(PROVABLE[n], n.bit_length() - 1),
+                 device_trace=lambda ctx, n: TABLE.module.generate_trace(ctx, _ops(PROVABLE[n]), degree_bits=n.bit_length() - 1),
+                 flip=lambda lt: (lt.RESULT + 5, 7))
+_stark, _reference_proof, _device_trace = TABLE.stark, TABLE.reference_proof, TABLE.device_trace
 
 
 @pytest.mark.gpu
@@ -301,25 +262,8 @@ def _device_trace(ctx, n):
 def test_proof_bytes_of_the_device_built_trace_equal_the_reference(gpu, hasher, num_challenges, n):
     """Keccak with 2 challenges would have quotient leaves of 4 elements, which KeccakHash<25> cannot hash (the reference panics): 1
     and 3 there."""
-    import plonky2_gpu_amd as pg
-    from oracle import accel
-    from plonky2_gpu_amd import logic_table as lt
-    from plonky2_gpu_amd import stark as pstark
-
-    exp = _reference_proof(hasher, num_challenges, n)
-    ns = pg.NativeStark(gpu, lt.stark_desc(n.bit_length() - 1, num_challenges, FP), hasher)
-    try:
-        d_trace = _device_trace(gpu, n)
-        data = ns.prove_bytes(d_trace, [])
-        assert data == exp
-        assert ns.prove_bytes(d_trace, []) == exp  # on recycled buffers
-    finally:
-        ns.close()
-    parsed = pstark.proof_from_bytes(data, ns.desc, hasher)
-    assert pstark.proof_to_bytes(parsed, ns.desc, hasher) == data
-    if (hasher, num_challenges) in (("poseidon", 2), ("keccak", 1)):
-        with accel.c_backend():
-            assert sr.verify(HASHERS[hasher], _stark(), num_challenges, FP, parsed, evaluator="closure")
+    verify = "closure" if (hasher, num_challenges) in (("poseidon", 2), ("keccak", 1)) else None
+    th.check_proof_bytes(TABLE, gpu, hasher, num_challenges, n, verify=verify)
 
 
 @pytest.mark.gpu
@@ -350,50 +294,18 @@ def test_compiled_in_units_gives_the_same_bytes(gpu):
 def test_quotient_polys_on_random_words_equal_the_reference(gpu):
     """uniformly random u64 words, the non-canonical ones (about 2^-32 of them) and a planted 2^64 - 1 and p included, in place of
     the LDE of the trace (every constraint non-zero), at the tight and at a padded column pitch"""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import logic_table as lt
-
     rng = np.random.default_rng(523)
     lde = rng.integers(0, 1 << 64, size=(COLUMNS, 64), dtype=np.uint64)
     lde[3, 0], lde[259, 1], lde[515, 2], lde[0, 3], lde[2, 63] = ONES, P, ONES, P + 1, ONES - 1
     alphas = [int(x) for x in rng.integers(0, 1 << 64, size=2, dtype=np.uint64)]
-    leaves = [[int(v) % P for v in row] for row in lde.T]
-    exp = np.array(sr.compute_quotient_polys(_stark(), 2, 5, 1, leaves, None, None, [], alphas), dtype=np.uint64)
-    assert exp.shape == (2, 64) and exp.all()
-    ns = pg.NativeStark(gpu, lt.stark_desc(5, 2, FP))
-    try:
-        for stride in (64, 64 + 6):
-            t = Strided(gpu, lde, stride)
-            got = ns.quotient_polys(t.ptr, None, stride, alphas, None, [])
-            assert (t.polys() == lde).all()
-            t.free()
-            bad = np.argwhere(got != exp)
-            assert bad.size == 0, ("column pitch", stride, "first (challenge, coefficient) that differs", bad[0].tolist(), len(bad))
-    finally:
-        ns.close()
+    th.check_quotient_polys(TABLE, gpu, lde, alphas)
 
 
 @pytest.mark.gpu
 def test_a_flipped_result_limb_gives_a_proof_the_verifier_rejects(gpu):
     """quotient_degree_factor 2 is a power of two: the reference's trim cannot fail, its prover returns a proof of the violated trace,
     and verification (tests/stark_verify.py, which accepts the proof of the untouched trace) fails at zeta. The device does the same."""
-    import plonky2_gpu_amd as pg
-    import stark_verify
-    from plonky2_gpu_amd import logic_table as lt
-
-    ns = pg.NativeStark(gpu, lt.stark_desc(5, 2, FP))
-    try:
-        d_trace = _device_trace(gpu, 32)
-        assert stark_verify.accepts(ns.desc, ns.prove_bytes(d_trace, []))
-        column, row = lt.RESULT + 5, 7
-        cell = d_trace.download(column * 32 + row, 1)
-        assert cell[0] == _reference(PROVABLE[32], 5)[column, row]
-        d_trace.upload(cell ^ np.uint64(1), column * 32 + row)
-        data = ns.prove_bytes(d_trace, [])
-    finally:
-        ns.close()
-    with pytest.raises(AssertionError, match="Mismatch between evaluation and opening"):
-        stark_verify.accepts(ns.desc, data)
+    th.check_flipped_cell_is_rejected(TABLE, gpu, "stark_verify")
 
 
 # ---------------------------------------------------------------- the lookup: a sponge-shaped looker and a plain one
@@ -433,11 +345,6 @@ def _ctl_looking_logic():
     res += [CtlColumn([(BYTES + 4 * k + j, 1 << (8 * j)) for j in range(4)]) for k in range(8)]
     res += [CtlColumn.single(XORED + k) for k in range(8)]
     return res
-
-
-class _System:
-    def __init__(self, tables, lookups):
-        self.tables, self.lookups, self.ctl_closures = tables, lookups, None
 
 
 @functools.lru_cache(maxsize=None)
@@ -484,7 +391,7 @@ def test_three_twcs_with_the_logic_lookup_equal_the_reference(gpu, hasher, num_c
     cols = _reference(20, 5)
     looker = _Looker()
     fps = [si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,), num_query_rounds=4, proof_of_work_bits=2) for _ in range(2)]
-    system = _System([looker, _stark()], lookups)
+    system = th.System([looker, _stark()], lookups)
     with accel.c_backend():
         exp = cr.proofs_bytes(HASHERS[hasher], cr.prove_tables(HASHERS[hasher], system, num_challenges, fps,
                                                                [looker_trace, [[int(v) for v in col] for col in cols]]))
@@ -506,31 +413,4 @@ def test_three_twcs_with_the_logic_lookup_equal_the_reference(gpu, hasher, num_c
 # ---------------------------------------------------------------- two contexts, two threads
 @pytest.mark.gpu
 def test_two_contexts_on_two_threads_build_and_prove(gpu):
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import logic_table as lt
-
-    exp = _reference_proof("poseidon", 2, 32)
-    ns = pg.NativeStark(gpu, lt.stark_desc(5, 2, FP))
-    other = pg.Context(0)
-    try:
-        alone = ns.prove_bytes(_device_trace(gpu, 32), [])
-        assert alone == exp
-        got, errors = [None, None], []
-
-        def work(k, ctx):
-            try:
-                for _ in range(2):
-                    got[k] = ns.prove_bytes(_device_trace(ctx, 32), [], ctx=ctx)
-            except Exception as e:  # noqa: BLE001
-                errors.append(e)
-
-        threads = [threading.Thread(target=work, args=(k, ctx)) for k, ctx in enumerate((gpu, other))]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        assert not errors, errors
-        assert got == [alone, alone]
-    finally:
-        ns.close()
-        other.close()
+    th.check_two_contexts_on_two_threads(TABLE, gpu)

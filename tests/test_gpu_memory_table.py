@@ -8,7 +8,6 @@ last ragged), 65537 (33 tiles, whose 256 x 33 digit counters take five blocks of
 import functools
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -16,17 +15,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import ctl_ref as cr  # noqa: E402
-import generic_prove_ref as gr  # noqa: E402
 import memory_table_instances as mi  # noqa: E402
 import memory_table_ref as mr  # noqa: E402
 import stark_instances as si  # noqa: E402
-import stark_ref as sr  # noqa: E402
+import table_harness as th  # noqa: E402
 from gpu_util import gpu  # noqa: E402,F401
 from strided import Strided  # noqa: E402
 
 P = 0xFFFFFFFF00000001
 ONES = (1 << 64) - 1
-HASHERS = {"poseidon": gr.PoseidonHasher(), "keccak": gr.KeccakHasher()}
+HASHERS = th.HASHERS
 COLUMNS = 26
 
 
@@ -248,34 +246,21 @@ def test_argument_refusals_launch_nothing(gpu):
 
 
 # ---------------------------------------------------------------- proofs
-FP = si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,))
+FP = th.FP
 PROVABLE = {32: ("provable", 10, 0), 64: ("provable", 13, 1)}  # 18 rows in 32; 21 rows in 64 (one bit above the need)
 
 
 @functools.lru_cache(maxsize=None)
-def _stark():
-    from plonky2_gpu_amd import memory_table as mt
-
-    instrs, immediates = mt.program()
-    return mr.MemoryTableStark(instrs, immediates)
-
-
-@functools.lru_cache(maxsize=None)
-def _reference_proof(hasher, num_challenges, n):
-    from oracle import accel
-
+def _provable_reference(n):
     cols = _reference(*PROVABLE[n])[0]
     assert cols.shape == (COLUMNS, n) and mr.satisfies_its_constraints(cols)  # on the CPU first: only some inputs are provable
-    trace = [[int(v) for v in col] for col in cols]
-    with accel.c_backend():
-        return sr.proof_bytes(HASHERS[hasher], sr.prove(HASHERS[hasher], _stark(), num_challenges, FP, trace, []))
+    return cols
 
 
-def _device_trace(ctx, n):
-    from plonky2_gpu_amd import memory_table as mt
-
-    family, num_ops, _ = PROVABLE[n]
-    return mt.generate_trace(ctx, _ops(family, num_ops), degree_bits=n.bit_length() - 1)
+TABLE = th.Table("memory_table", mr.MemoryTableStark, COLUMNS, (32, 64), reference_trace=_provable_reference,
+                 device_trace=lambda ctx, n: TABLE.module.generate_trace(ctx, _ops(*PROVABLE[n][:2]), degree_bits=n.bit_length() - 1),
+                 flip=lambda mt: (mt.value_limb(2), 1))
+_stark, _reference_proof, _device_trace = TABLE.stark, TABLE.reference_proof, TABLE.device_trace
 
 
 @pytest.mark.gpu
@@ -284,21 +269,7 @@ def _device_trace(ctx, n):
 def test_proof_bytes_of_the_device_built_trace_equal_the_reference(gpu, hasher, num_challenges, n):
     """Keccak with 2 challenges would have quotient leaves of 4 elements, which KeccakHash<25> cannot hash (the reference panics): 1
     and 3 there. The padding rows stand in the middle of both traces."""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import memory_table as mt
-    from plonky2_gpu_amd import stark as pstark
-
-    exp = _reference_proof(hasher, num_challenges, n)
-    ns = pg.NativeStark(gpu, mt.stark_desc(n.bit_length() - 1, num_challenges, FP), hasher)
-    try:
-        d_trace = _device_trace(gpu, n)
-        data = ns.prove_bytes(d_trace, [])
-        assert data == exp
-        assert ns.prove_bytes(d_trace, []) == exp  # on recycled buffers
-    finally:
-        ns.close()
-    parsed = pstark.proof_from_bytes(data, ns.desc, hasher)
-    assert pstark.proof_to_bytes(parsed, ns.desc, hasher) == data
+    th.check_proof_bytes(TABLE, gpu, hasher, num_challenges, n)
 
 
 @pytest.mark.gpu
@@ -319,29 +290,12 @@ def test_the_compiled_kernel_gives_the_same_bytes(gpu):
 def test_quotient_polys_on_random_words_equal_the_reference(gpu):
     """uniformly random words in place of the LDEs of the trace and of the two permutation Zs (every constraint non-zero), at the
     tight and at a padded column pitch"""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import memory_table as mt
-
     rng = np.random.default_rng(2226)
     lde = rng.integers(0, P, size=(COLUMNS, 64), dtype=np.uint64)
     zs = rng.integers(0, P, size=(2, 64), dtype=np.uint64)
     alphas = [int(x) for x in rng.integers(0, P, size=2, dtype=np.uint64)]
     sets = [[tuple(int(x) for x in rng.integers(0, P, size=2, dtype=np.uint64)) for _ in range(2)] for _ in range(2)]
-    leaves = lambda a: [[int(v) for v in row] for row in a.T]  # noqa: E731
-    exp = np.array(sr.compute_quotient_polys(_stark(), 2, 5, 1, leaves(lde), leaves(zs), sets, [], alphas), dtype=np.uint64)
-    assert exp.shape == (2, 64) and exp.all()
-    ns = pg.NativeStark(gpu, mt.stark_desc(5, 2, FP))
-    try:
-        for stride in (64, 64 + 6):
-            t, z = Strided(gpu, lde, stride), Strided(gpu, zs, stride)
-            got = ns.quotient_polys(t.ptr, z.ptr, stride, alphas, sets, [])
-            assert (t.polys() == lde).all() and (z.polys() == zs).all()
-            t.free()
-            z.free()
-            bad = np.argwhere(got != exp)
-            assert bad.size == 0, ("column pitch", stride, "first (challenge, coefficient) that differs", bad[0].tolist(), len(bad))
-    finally:
-        ns.close()
+    th.check_quotient_polys(TABLE, gpu, lde, alphas, zs, sets)
 
 
 @pytest.mark.gpu
@@ -349,22 +303,9 @@ def test_a_flipped_value_limb_gives_a_proof_the_verifier_rejects(gpu):
     """row 1 is the read of address 0 behind its write: with another limb the value constraints of rows 0 and 1 fail.
     quotient_degree_factor 2 is a power of two: the reference's trim cannot fail, its prover returns a proof of the violated trace,
     and verification fails at zeta. The device does the same."""
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import memory_table as mt
-    from plonky2_gpu_amd import stark as pstark
-
-    ns = pg.NativeStark(gpu, mt.stark_desc(5, 2, FP))
-    try:
-        d_trace = _device_trace(gpu, 32)
-        column, row = mt.value_limb(2), 1
-        cell = d_trace.download(column * 32 + row, 1)
-        assert cell[0] == _reference(*PROVABLE[32])[0][column, row] and _reference(*PROVABLE[32])[0][mt.IS_READ, row] == 1
-        d_trace.upload(cell ^ np.uint64(1), column * 32 + row)
-        parsed = pstark.proof_from_bytes(ns.prove_bytes(d_trace, []), ns.desc)
-    finally:
-        ns.close()
-    with pytest.raises(AssertionError, match="Mismatch between evaluation and opening"):
-        sr.verify(HASHERS["poseidon"], _stark(), 2, FP, parsed)
+    column, row = TABLE.flip(TABLE.module)
+    assert _provable_reference(32)[TABLE.module.IS_READ, row] == 1
+    th.check_flipped_cell_is_rejected(TABLE, gpu, "stark_ref")
 
 
 # ---------------------------------------------------------------- two tables and the cross-table lookup
@@ -383,11 +324,6 @@ class _Cpu:
     @staticmethod
     def closure(F, local, nxt, pis, consumer):
         consumer.constraint(F.mul(local[13], F.sub(local[13], F.one)))
-
-
-class _System:
-    def __init__(self, tables, lookups):
-        self.tables, self.lookups, self.ctl_closures = tables, lookups, None
 
 
 @pytest.mark.gpu
@@ -411,7 +347,7 @@ def test_two_tables_with_the_memory_lookup_equal_the_reference(gpu):
     lookups = [CrossTableLookup([TableWithColumns(0, [CtlColumn.single(c) for c in range(13)], CtlColumn.single(13))],
                                 TableWithColumns(1, mt.ctl_data(), mt.ctl_filter()))]
     fps = [si.fri_params(rate_bits=1, cap_height=1, arity_bits=(2,), num_query_rounds=4, proof_of_work_bits=2) for _ in range(2)]
-    system = _System([cpu, _stark()], lookups)
+    system = th.System([cpu, _stark()], lookups)
     with accel.c_backend():
         exp = cr.proofs_bytes(HASHERS["poseidon"], cr.prove_tables(HASHERS["poseidon"], system, 1, fps, [cpu_trace, [[int(v) for v in col] for col in cols]]))
     desc = StarkTablesDesc([StarkDesc(4, 14, 0, 3, 1, fps[0], cpu.instrs, cpu.immediates), mt.stark_desc(5, 1, fps[1])], lookups)
@@ -429,31 +365,4 @@ def test_two_tables_with_the_memory_lookup_equal_the_reference(gpu):
 # ---------------------------------------------------------------- two contexts, two threads
 @pytest.mark.gpu
 def test_two_contexts_on_two_threads_build_and_prove(gpu):
-    import plonky2_gpu_amd as pg
-    from plonky2_gpu_amd import memory_table as mt
-
-    exp = _reference_proof("poseidon", 2, 32)
-    ns = pg.NativeStark(gpu, mt.stark_desc(5, 2, FP))
-    other = pg.Context(0)
-    try:
-        alone = ns.prove_bytes(_device_trace(gpu, 32), [])
-        assert alone == exp
-        got, errors = [None, None], []
-
-        def work(k, ctx):
-            try:
-                for _ in range(2):
-                    got[k] = ns.prove_bytes(_device_trace(ctx, 32), [], ctx=ctx)
-            except Exception as e:  # noqa: BLE001
-                errors.append(e)
-
-        threads = [threading.Thread(target=work, args=(k, ctx)) for k, ctx in enumerate((gpu, other))]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        assert not errors, errors
-        assert got == [alone, alone]
-    finally:
-        ns.close()
-        other.close()
+    th.check_two_contexts_on_two_threads(TABLE, gpu)

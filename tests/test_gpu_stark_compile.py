@@ -36,23 +36,10 @@ import test_ctl_fuzz as tcf  # noqa: E402  (cf.coverage is pinned there)
 import test_gpu_ctl as tgc  # noqa: E402  (_check_ctl_quotient, _reference: the reference proofs, proved once)
 import test_gpu_stark as tgs  # noqa: E402  (_reference_proof, _trace: the reference proofs, proved once)
 import test_gpu_stark_fuzz as tgsf  # noqa: E402  (_desc)
-from gpu_util import gpu  # noqa: E402,F401
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 from strided import Strided  # noqa: E402
 
 P = sr.P
-
-
-@pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile"""
-    cache = str(tmp_path_factory.mktemp("stark_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 def _objects(cache):

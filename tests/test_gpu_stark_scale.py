@@ -40,7 +40,7 @@ import representatives as rep  # noqa: E402
 import stark_instances as si  # noqa: E402
 import stark_ref as sr  # noqa: E402
 import stark_scale as ss  # noqa: E402
-from gpu_util import gpu  # noqa: E402,F401
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 from stark_scale import bkt, bsp  # noqa: E402
 from strided import Strided  # noqa: E402
 
@@ -50,16 +50,9 @@ _BUILT, _BYTES = {}, {}  # per case: (description, trace in HBM, public inputs) 
 
 
 @pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile; behind the module the traces it kept in HBM are freed"""
-    cache = str(tmp_path_factory.mktemp("stark_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
+def built_traces_freed():
+    """behind the module the traces it kept in HBM are freed"""
+    yield
     for built in _BUILT.values():
         for d_trace in built[1] if isinstance(built[1], list) else [built[1]]:
             d_trace.free()

@@ -33,23 +33,10 @@ import test_gpu_ctl as tgc  # noqa: E402  (_reference: the reference proofs, pro
 import test_gpu_memory_table as tgm  # noqa: E402  (_Cpu, _ops: the two-table system of the memory lookup)
 import test_gpu_stark as tgs  # noqa: E402  (_reference_proof, _trace: the reference proofs, proved once)
 import test_gpu_stark_fuzz as tgsf  # noqa: E402  (_desc)
-from gpu_util import gpu  # noqa: E402,F401
+from gpu_util import gpu, kernel_cache  # noqa: E402,F401
 from strided import Strided  # noqa: E402
 
 P = sr.P
-
-
-@pytest.fixture(scope="module", autouse=True)
-def kernel_cache(tmp_path_factory):
-    """the library reads the variable at every compile"""
-    cache = str(tmp_path_factory.mktemp("stark_units_kernel_cache"))
-    saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-    os.environ["PLONKY2_HIP_KERNEL_CACHE"] = cache
-    yield cache
-    if saved is None:
-        os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-    else:
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = saved
 
 
 def _objects(cache):

@@ -36,7 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 
 import plonky2_gpu_amd as pg
-from bench_logic_table import _TemporaryKernelCache, fast_config_fri_params, ops_for, stats, timed_alternating
+from bench_common import TemporaryKernelCache, fast_config_fri_params, stats
+from bench_logic_table import ops_for, timed_alternating
 from plonky2_gpu_amd import _lib
 from plonky2_gpu_amd import keccak_sponge_table as ks
 from plonky2_gpu_amd import logic_table as lt
@@ -181,7 +182,7 @@ def measure_chain(ctx, bits, reps, serial_budget_s):
 
 
 def measure_prove(ctx, bits, reps, verify):
-    """interpreted against compiled in units, alternating, inside a _TemporaryKernelCache: the first size carries the cold compile"""
+    """interpreted against compiled in units, alternating, inside a TemporaryKernelCache: the first size carries the cold compile"""
     desc = ks.stark_desc(bits, 2, fast_config_fri_params(bits))
     words, data = operations(1 << bits, ONE_BLOCK_LEN)
     d_trace = ks.generate_trace(ctx, words, data, degree_bits=bits)
@@ -246,7 +247,7 @@ def main():
     for bits in sorted(a.chain_bits):
         res["chain"]["2^%d" % bits] = measure_chain(ctx, bits, a.reps, a.serial_budget_s)
         print("chain 2^%d" % bits, json.dumps(res["chain"]["2^%d" % bits]), file=sys.stderr, flush=True)
-    with _TemporaryKernelCache():
+    with TemporaryKernelCache("keccak_sponge_table"):
         for k, bits in enumerate(sorted(a.prove_bits)):
             res["prove"]["2^%d" % bits] = measure_prove(ctx, bits, a.reps, verify=k == 0)
             print("prove 2^%d" % bits, json.dumps(res["prove"]["2^%d" % bits]), file=sys.stderr, flush=True)

@@ -29,7 +29,6 @@ inputs_for and the parameters from here. One JSON line on stdout and in --out (d
 import argparse
 import json
 import os
-import shutil
 import subprocess
 import sys
 import tempfile
@@ -41,24 +40,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 import plonky2_gpu_amd as pg
+from bench_common import TemporaryKernelCache, fast_config_fri_params, stats
 from plonky2_gpu_amd import _lib
 from plonky2_gpu_amd import keccak_table as kt
 
 SPEC_BYTES_PER_S = 8e12  # the 8 TB/s of the MI355X's specification
-
-
-def fast_config_fri_params(degree_bits):
-    """FriConfig::fri_params of standard_fast_config (plonky2/src/fri/reduction_strategies.rs:38-49)"""
-    rate_bits, cap_height, arity, final_poly_bits = 1, 4, 4, 5
-    arities, db = [], degree_bits
-    while db > final_poly_bits and db + rate_bits - arity >= cap_height:
-        arities.append(arity)
-        db -= arity
-    return dict(rate_bits=rate_bits, cap_height=cap_height, proof_of_work_bits=16, num_query_rounds=84, reduction_arity_bits=arities, hiding=False)
-
-
-def stats(ms):
-    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
 def inputs_for(bits):
@@ -130,24 +116,6 @@ def measure_prove(ctx, bits, reps):
     return dict(stats(ms), rows=n, proof_bytes=len(first), program_instructions=int(desc.instrs.shape[0]), stage_ms={k: round(v, 3) for k, v in timing.items()})
 
 
-class _TemporaryKernelCache:
-    """an empty kernel cache of its own while the block runs; AMD_COMGR_CACHE off, so that a cold compile is hiprtc's own time"""
-
-    def __enter__(self):
-        self.dir = tempfile.mkdtemp(prefix="keccak_table_kernel_cache_")
-        self.saved = {k: os.environ.get(k) for k in ("PLONKY2_HIP_KERNEL_CACHE", "AMD_COMGR_CACHE")}
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"], os.environ["AMD_COMGR_CACHE"] = self.dir, "0"
-        return self.dir
-
-    def __exit__(self, *exc):
-        for k, v in self.saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        shutil.rmtree(self.dir, ignore_errors=True)
-
-
 def _precompile_desc(which):
     if which == "keccak":
         return kt.stark_desc(12, 2, fast_config_fri_params(12))
@@ -175,7 +143,7 @@ def measure_precompile(which, caps):
     out = {}
     for cap in caps:
         name = "single kernel" if cap < 0 else str(cap)
-        with _TemporaryKernelCache(), tempfile.TemporaryDirectory(prefix="comgr_cache_") as comgr:
+        with TemporaryKernelCache("keccak_table", {"AMD_COMGR_CACHE": "0"}), tempfile.TemporaryDirectory(prefix="comgr_cache_") as comgr:
             env = dict(os.environ, AMD_COMGR_CACHE_DIR=comgr)
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--precompile-child", which, str(cap)], env=env, capture_output=True, text=True)
             if r.returncode != 0:
@@ -193,7 +161,7 @@ def _verified(desc, data):
 
 
 def measure_compiled(ctx, bits, reps, unit_instrs, verify=True):
-    """interpreted against compiled in units, alternating, inside a _TemporaryKernelCache: the first size measured in it carries the
+    """interpreted against compiled in units, alternating, inside a TemporaryKernelCache: the first size measured in it carries the
     cold compile time (the units' sources do not depend on the number of rows), every size the warm one"""
     desc = kt.stark_desc(bits, 2, fast_config_fri_params(bits))
     d_trace = kt.generate_trace(ctx, inputs_for(bits), bits)
@@ -262,10 +230,10 @@ def main_compiled(a):
                yardstick="the interpreter (stark_quotient_values_kernel) in the same run: calls of the two handles alternate",
                prove_config="KeccakStark: 2430 columns, degree 3, Poseidon, standard_fast_config; trace built on the device and resident")
     for cap in a.caps or []:
-        with _TemporaryKernelCache():
+        with TemporaryKernelCache("keccak_table", {"AMD_COMGR_CACHE": "0"}):
             res["caps"][str(cap)] = {"2^%d" % bits: measure_compiled(ctx, bits, a.reps, cap, verify=False) for bits in a.prove_bits}
         print("cap", cap, json.dumps(res["caps"][str(cap)]), file=sys.stderr, flush=True)
-    with _TemporaryKernelCache():
+    with TemporaryKernelCache("keccak_table", {"AMD_COMGR_CACHE": "0"}):
         for bits in a.prove_bits:
             res["prove"]["2^%d" % bits] = measure_compiled(ctx, bits, a.reps, a.unit_instrs)
             print("2^%d" % bits, json.dumps(res["prove"]["2^%d" % bits]), file=sys.stderr, flush=True)

@@ -24,9 +24,7 @@ and in --out (default profiles/logic_table.json).
 import argparse
 import json
 import os
-import shutil
 import sys
-import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,25 +33,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 import plonky2_gpu_amd as pg
+from bench_common import TemporaryKernelCache, fast_config_fri_params, stats
 from plonky2_gpu_amd import _lib
 from plonky2_gpu_amd import keccak_table as kt
 from plonky2_gpu_amd import logic_table as lt
 
 SPEC_BYTES_PER_S = 8e12  # the 8 TB/s of the MI355X's specification
-
-
-def fast_config_fri_params(degree_bits):
-    """FriConfig::fri_params of standard_fast_config (plonky2/src/fri/reduction_strategies.rs:38-49)"""
-    rate_bits, cap_height, arity, final_poly_bits = 1, 4, 4, 5
-    arities, db = [], degree_bits
-    while db > final_poly_bits and db + rate_bits - arity >= cap_height:
-        arities.append(arity)
-        db -= arity
-    return dict(rate_bits=rate_bits, cap_height=cap_height, proof_of_work_bits=16, num_query_rounds=84, reduction_arity_bits=arities, hiding=False)
-
-
-def stats(ms):
-    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(min(ms)), 4), "max_ms": round(float(max(ms)), 4)}
 
 
 def ops_for(bits):
@@ -155,25 +140,8 @@ def measure_trace(ctx, bits, reps, upload):
     return res
 
 
-class _TemporaryKernelCache:
-    """an empty kernel cache of its own while the block runs"""
-
-    def __enter__(self):
-        self.dir = tempfile.mkdtemp(prefix="logic_table_kernel_cache_")
-        self.saved = os.environ.get("PLONKY2_HIP_KERNEL_CACHE")
-        os.environ["PLONKY2_HIP_KERNEL_CACHE"] = self.dir
-        return self.dir
-
-    def __exit__(self, *exc):
-        if self.saved is None:
-            os.environ.pop("PLONKY2_HIP_KERNEL_CACHE", None)
-        else:
-            os.environ["PLONKY2_HIP_KERNEL_CACHE"] = self.saved
-        shutil.rmtree(self.dir, ignore_errors=True)
-
-
 def measure_prove(ctx, bits, reps, verify):
-    """interpreted against compiled in units, alternating, inside a _TemporaryKernelCache: the first size carries the cold compile"""
+    """interpreted against compiled in units, alternating, inside a TemporaryKernelCache: the first size carries the cold compile"""
     desc = lt.stark_desc(bits, 2, fast_config_fri_params(bits))
     d_trace = lt.generate_trace(ctx, ops_for(bits), bits)
     interpreted, compiled = pg.NativeStark(ctx, desc), pg.NativeStark(ctx, desc)
@@ -236,7 +204,7 @@ def main():
     for bits in sorted(a.bits):
         res["trace"]["2^%d" % bits] = measure_trace(ctx, bits, a.reps, bits <= a.upload_max_bits)
         print("2^%d" % bits, json.dumps(res["trace"]["2^%d" % bits]), file=sys.stderr, flush=True)
-    with _TemporaryKernelCache():
+    with TemporaryKernelCache("logic_table"):
         for k, bits in enumerate(sorted(a.prove_bits)):
             res["prove"]["2^%d" % bits] = measure_prove(ctx, bits, a.reps, verify=k == 0)
             print("prove 2^%d" % bits, json.dumps(res["prove"]["2^%d" % bits]), file=sys.stderr, flush=True)

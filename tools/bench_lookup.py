@@ -30,26 +30,13 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 import plonky2_gpu_amd as pg
+from bench_common import fast_config_fri_params, stats
 from plonky2_gpu_amd import _lib, lookup
 from plonky2_gpu_amd import stark as pstark
 
 P = 0xFFFFFFFF00000001
 C0, V, PV, PT, F4, F5 = range(6)
 LOOKUPS = [(V, C0, PV, PT)]
-
-
-def fast_config_fri_params(degree_bits):
-    """FriConfig::fri_params of standard_fast_config (plonky2/src/fri/reduction_strategies.rs:38-49)"""
-    rate_bits, cap_height, arity, final_poly_bits = 1, 4, 4, 5
-    arities, db = [], degree_bits
-    while db > final_poly_bits and db + rate_bits - arity >= cap_height:
-        arities.append(arity)
-        db -= arity
-    return dict(rate_bits=rate_bits, cap_height=cap_height, proof_of_work_bits=16, num_query_rounds=84, reduction_arity_bits=arities, hiding=False)
-
-
-def stats(ms):
-    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
 def serial_merge(s, t):

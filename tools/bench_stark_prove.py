@@ -57,21 +57,12 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 import plonky2_gpu_amd as pg
+from bench_common import fast_config_fri_params
 from plonky2_gpu_amd import _lib
 from plonky2_gpu_amd import stark as pstark
 
 P = 0xFFFFFFFF00000001
 WIDE_TRIPLES = 33
-
-
-def fast_config_fri_params(degree_bits):
-    """FriConfig::fri_params of standard_fast_config (plonky2/src/fri/reduction_strategies.rs:38-49)"""
-    rate_bits, cap_height, arity, final_poly_bits = 1, 4, 4, 5
-    arities, db = [], degree_bits
-    while db > final_poly_bits and db + rate_bits - arity >= cap_height:
-        arities.append(arity)
-        db -= arity
-    return dict(rate_bits=rate_bits, cap_height=cap_height, proof_of_work_bits=16, num_query_rounds=84, reduction_arity_bits=arities, hiding=False)
 
 
 def fibonacci(ctx, degree_bits):
