@@ -1123,7 +1123,8 @@ const char *cudaGetErrorString(int code);
 
 /* Test hook: element-wise field op on device arrays (op: 0 add, 1 sub, 2 mul, 3 neg, 4 x^7,
  * 5 a + b*b, 6 a * 2^(b mod 192), 7 a + canon(b), 8-16 internal variants, 17 a + (b mod 2^63) * 2^32, 18-27 the grouped
- * forms with deferred corrections); output canonical. d_b may be NULL for unary ops. Ops 100-109: the register-level radix
+ * forms with deferred corrections, 28-30 the canonical form of a, b, a ^ b as a group with the subtraction deferred: stored as the
+ * group left it); output canonical. d_b may be NULL for unary ops. Ops 100-109: the register-level radix
  * routines of the NTT passes on vectors of sixteen elements (n = 16 x vectors; d_b unused), see csrc/probes.hip. */
 GlError gl_debug_field_op(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, uint64_t n, void *ctx);
 /* Measurement hook: a plain streaming copy kernel (16 B per lane, asynchronous on ctx->stream) — the bandwidth a

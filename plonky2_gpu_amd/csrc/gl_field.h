@@ -325,20 +325,28 @@ __device__ __forceinline__ uint64_t add_fix(uint64_t r, rare_mask f) {
     return r;
 }
 
-__device__ __forceinline__ uint64_t sub_f(uint64_t a, uint64_t b, rare_mask &f) {
+// a - b in FOUR instructions. With d = a - b (mod 2^64) and its borrow B the result is d - B e = d - B 2^32 + B: the two words are corrected
+// separately while B is still in VCC, dh - B and dl + B, instead of materialising B e in a register and subtracting it with a second
+// borrow chain (five instructions and a temporary). What couples the words is the carry of dl + B into dh, which needs dl = 2^32 - 1:
+// probability 2^-32 per lane, the class of the second borrow, and deferred with it. Two masks:
+//   fl: dl + B carried (the new dl is 0): the true result is r + 2^32 (if dh - B borrowed as well, that borrow is cancelled: no "- e")
+//   fh: dh - B borrowed. In the lanes of fh that are not in fl this is the second borrow: the true result is r - e, as before
+// Both corrections read the VCC that a vector instruction wrote (interlocked on gfx950, see mul) and write scalar pairs that only
+// the scalar ORs behind the group's fence read.
+__device__ __forceinline__ uint64_t sub_f(uint64_t a, uint64_t b, rare_mask &fh, rare_mask &fl) {
     uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), bl = (uint32_t)b, bh = (uint32_t)(b >> 32);
-    uint32_t rl, rh, t;
+    uint32_t rl, rh;
     asm("v_sub_co_u32_e32 %0, vcc, %4, %6\n\t"
-        "v_subb_co_u32_e32 %1, vcc, %5, %7, vcc\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"                    // borrow: -2^64 = -(2^32 - 1)
-        "v_sub_co_u32_e32 %0, vcc, %0, %2\n\t"
-        "v_subbrev_co_u32_e64 %1, %3, 0, %1, vcc"                  // borrow -> the mask
-        : "=&v"(rl), "=&v"(rh), "=&v"(t), "=&s"(f)
+        "v_subb_co_u32_e32 %1, vcc, %5, %7, vcc\n\t"             // borrow B
+        "v_subbrev_co_u32_e64 %1, %2, 0, %1, vcc\n\t"            // dh - B, its borrow -> fh (VCC unchanged)
+        "v_addc_co_u32_e64 %0, %3, 0, %0, vcc"                     // dl + B, its carry -> fl
+        : "=&v"(rl), "=&v"(rh), "=&s"(fh), "=&s"(fl)
         : "v"(al), "v"(ah), "v"(bl), "v"(bh)
         : "vcc");
     return ((uint64_t)rh << 32) | rl;
 }
-__device__ __forceinline__ uint64_t sub_fix(uint64_t r, rare_mask f) {
+// the deferred "- e once more" alone: the second borrow of the shifts (mul_pow2_f)
+__device__ __forceinline__ uint64_t borrow_fix(uint64_t r, rare_mask f) {
     uint32_t rl = (uint32_t)r, rh = (uint32_t)(r >> 32), t;
     asm volatile("v_cndmask_b32_e64 %2, 0, -1, %3\n\t"
                  "v_sub_co_u32_e32 %0, vcc, %0, %2\n\t"
@@ -347,6 +355,45 @@ __device__ __forceinline__ uint64_t sub_fix(uint64_t r, rare_mask f) {
                  : "s"(f)
                  : "vcc");
     return ((uint64_t)rh << 32) | rl;
+}
+// the corrections of sub_f: + 2^32 in the lanes of fl (the high word cannot wrap past a value it should have: the missed carry is
+// the only thing wrong there), - e in the lanes of fh that are not in fl (the wrapped difference is above 2^64 - e: no third borrow)
+__device__ __forceinline__ uint64_t sub_fix(uint64_t r, rare_mask fh, rare_mask fl) {
+    uint32_t rl = (uint32_t)r, rh = (uint32_t)(r >> 32), t;
+    asm volatile("s_andn2_b64 vcc, %3, %4\n\t"
+                 "s_nop 1\n\t"
+                 "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"          // e where the second borrow is pending
+                 "v_addc_co_u32_e64 %1, vcc, 0, %1, %4\n\t"      // the missed carry
+                 "v_sub_co_u32_e32 %0, vcc, %0, %2\n\t"
+                 "v_subbrev_co_u32_e32 %1, vcc, 0, %1, vcc"
+                 : "+v"(rl), "+v"(rh), "=&v"(t)
+                 : "s"(fh), "s"(fl)
+                 : "vcc");
+    return ((uint64_t)rh << 32) | rl;
+}
+
+// Canonical form of a value that is about to be stored, rare path deferred: x >= p needs a high word of 2^32 - 1 (2^-32 per lane for
+// what add_f / sub_f / mul_f hand out), so the hot path is ONE compare that flags a superset of x >= p, and the exact conditional
+// subtraction waits behind the group's branch (gl::canon compiles to a 64-bit compare, a 64-bit add and two selects per value).
+// NOT used by the NTT passes: in their tails the branch per group of stores cost more than the 64 instructions saved (LABNOTES 17).
+// Kept for gl_debug_field_op 28-30 and tests/test_gpu_canon_store.py, for whoever finds a place with larger groups.
+__device__ __forceinline__ void canon_f(uint64_t x, rare_mask &f) {
+    asm("v_cmp_eq_u32_e64 %0, -1, %1" : "=&s"(f) : "v"((uint32_t)(x >> 32)));
+}
+// The exact conditional subtraction in the flagged lanes, on the register pair as it stands and with the temporaries of the
+// multiplication (v32, v33, v42): no register of its own, which matters where the cold block sits inside a loop that uses every vector
+// register. x - p = x + e (mod 2^64), and x + e carries out iff x >= p.
+__device__ __forceinline__ uint64_t canon_fix(uint64_t x, rare_mask f) {
+    asm volatile("v_mov_b32_e32 v42, -1\n\t"
+                 "v_mad_u64_u32 v[32:33], vcc, v42, 1, %0\n\t"   // x + e: only its carry is wanted
+                 "s_and_b64 vcc, vcc, %1\n\t"
+                 "s_nop 1\n\t"
+                 "v_cndmask_b32_e64 v42, 0, -1, vcc\n\t"
+                 "v_mad_u64_u32 %0, vcc, v42, 1, %0"
+                 : "+v"(x)
+                 : "s"(f)
+                 : "vcc", "v32", "v33", "v42");
+    return x;
 }
 
 __device__ __forceinline__ uint64_t mul_f(uint64_t a, uint64_t b, rare_mask &f) {
@@ -384,23 +431,22 @@ __device__ __forceinline__ uint64_t mul_fix(uint64_t r, rare_mask f) {
     return ((uint64_t)rh << 32) | rl;
 }
 
-// One radix-2 butterfly, s = a + c and d = a - c (NEG: c - a), as ONE block with both rare paths deferred: the nine instructions of
-// add_f and sub_f without the wait state the compiler puts between two asm statements.
+// One radix-2 butterfly, s = a + c and d = a - c (NEG: c - a), as ONE block with both rare paths deferred: the eight instructions of
+// add_f and sub_f without the wait state the compiler puts between two asm statements. fh / fl: sub_f's two masks.
 template <bool NEG>
-__device__ __forceinline__ void bfly_f(uint64_t a, uint64_t c, uint64_t &s, uint64_t &d, rare_mask &fa, rare_mask &fs) {
+__device__ __forceinline__ void bfly_f(uint64_t a, uint64_t c, uint64_t &s, uint64_t &d, rare_mask &fa, rare_mask &fh, rare_mask &fl) {
     const uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), cl = (uint32_t)c, ch = (uint32_t)(c >> 32);
-    uint32_t dl, dh, t;
+    uint32_t dl, dh;
     uint64_t r;
     asm("v_add_co_u32_e32 v32, vcc, %6, %8\n\t"
         "v_addc_co_u32_e32 v33, vcc, %7, %9, vcc\n\t"
         "v_cndmask_b32_e64 v42, 0, -1, vcc\n\t"
-        "v_mad_u64_u32 %0, %4, v42, 1, v[32:33]\n\t"             // s, second wrap -> fa
+        "v_mad_u64_u32 %0, %3, v42, 1, v[32:33]\n\t"             // s, second wrap -> fa
         "v_sub_co_u32_e32 %1, vcc, %10, %12\n\t"
-        "v_subb_co_u32_e32 %2, vcc, %11, %13, vcc\n\t"
-        "v_cndmask_b32_e64 %3, 0, -1, vcc\n\t"
-        "v_sub_co_u32_e32 %1, vcc, %1, %3\n\t"
-        "v_subbrev_co_u32_e64 %2, %5, 0, %2, vcc"                   // d, second borrow -> fs
-        : "=&v"(r), "=&v"(dl), "=&v"(dh), "=&v"(t), "=&s"(fa), "=&s"(fs)
+        "v_subb_co_u32_e32 %2, vcc, %11, %13, vcc\n\t"           // borrow B
+        "v_subbrev_co_u32_e64 %2, %4, 0, %2, vcc\n\t"            // dh - B, its borrow -> fh
+        "v_addc_co_u32_e64 %1, %5, 0, %1, vcc"                     // dl + B, its carry -> fl
+        : "=&v"(r), "=&v"(dl), "=&v"(dh), "=&s"(fa), "=&s"(fh), "=&s"(fl)
         : "v"(al), "v"(ah), "v"(cl), "v"(ch), "v"(NEG ? cl : al), "v"(NEG ? ch : ah), "v"(NEG ? al : cl), "v"(NEG ? ah : ch)
         : "vcc", "v32", "v33", "v42");
     s = r;
@@ -414,7 +460,7 @@ __device__ __forceinline__ uint64_t mul_pow2_f(uint64_t x, rare_mask &f);
 template <int K>
 __device__ __forceinline__ uint64_t mul_pow2_fix(uint64_t r, rare_mask f) {
     constexpr int Q = K / 32, S = K % 32;
-    if constexpr (S != 0 && Q >= 1) return sub_fix(r, f);  // the deferred correction is "- e once more", as sub's
+    if constexpr (S != 0 && Q >= 1) return borrow_fix(r, f);  // the deferred correction is "- e once more"
     return r;
 }
 
@@ -441,9 +487,8 @@ __device__ __forceinline__ uint64_t masked_const(rare_mask f) {
                  : "i"((uint32_t)C), "i"((uint32_t)(C >> 32)), "s"(f));
     return ((uint64_t)rh << 32) | rl;
 }
-// (2^32 - 1) 2^k mod p, canonical, for 0 <= k < 96
-constexpr uint64_t eps_times_pow2(int k) {
-    uint64_t x = 0xFFFFFFFFull;
+// x 2^k mod p, canonical, for canonical x
+constexpr uint64_t times_pow2(uint64_t x, int k) {
     for (int i = 0; i < k; i++) {
         const bool top = x >> 63;
         x <<= 1;                       // 2 x mod 2^64; the lost 2^64 = 2^32 - 1 (mod p)
@@ -452,11 +497,26 @@ constexpr uint64_t eps_times_pow2(int k) {
     }
     return x;
 }
+// (2^32 - 1) 2^k mod p and 2^(32 + k) mod p: what a pending "- e" / "+ 2^32" of sub_f has become behind a shift by k (0 <= k < 96)
+constexpr uint64_t eps_times_pow2(int k) { return times_pow2(0xFFFFFFFFull, k); }
+constexpr uint64_t carry_times_pow2(int k) { return times_pow2(1ull << 32, k); }
+// the pending corrections of a difference that went through a shift by K after sub_f / bfly_f (the shift is linear and exact for any
+// representative): - e 2^K in the lanes of fh, + 2^(32 + K) in the lanes of fl. Cold: full add / sub.
+template <int K, uint64_t WRONG = 0, uint64_t WRONG_CARRY = 0>
+__device__ __forceinline__ uint64_t sub_fix_shifted(uint64_t r, rare_mask fh, rare_mask fl);
 
 // did any lane of the wave flag any operation of the group? (uniform: the masks are scalar registers)
 // A MACRO, not a function: the hint must sit in the `if` itself. (Returned from an inline function it is dropped before inlining, the
 // compiler lays the correction block out as the fall-through, and the hot path pays a TAKEN branch over it at every group.)
 #define GL_RARE_ANY(m) __builtin_expect((m) != 0, 0)
+
+template <int K, uint64_t WRONG, uint64_t WRONG_CARRY>
+__device__ __forceinline__ uint64_t sub_fix_shifted(uint64_t r, rare_mask fh, rare_mask fl) {
+    // a lane in both masks takes both: there dh - B wrapped as well, and + 2^32 - e = + 1 is what the missed carry is worth mod p
+    // (sub_fix, which works on the bits, lets the carry's wrap of the high word cancel the borrow instead)
+    r = sub(r, masked_const<eps_times_pow2(K) + WRONG>(fh));   // WRONG, WRONG_CARRY: the tests' negative controls only
+    return add(r, masked_const<carry_times_pow2(K) + WRONG_CARRY>(fl));
+}
 
 // acc + x*y (goldilocks_field.rs:119-123): the multiplication followed by the addition, 16 VALU; the fused
 // arrangement this replaced (the addend riding on the first multiply-adds) took 22.

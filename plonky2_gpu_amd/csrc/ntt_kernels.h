@@ -102,6 +102,9 @@ __device__ __forceinline__ void twiddle_chain(const PassParams &p, uint32_t tid,
 #ifndef RARE_STAGE_COMBINED
 #define RARE_STAGE_COMBINED 1
 #endif
+#ifndef RARE_STAGE_CHUNK
+#define RARE_STAGE_CHUNK 4   // butterflies per group of the combined stage
+#endif
 // NBLK adjacent blocks of 2^D slots starting at BASE go through stage s TOGETHER (their butterflies are independent: larger groups)
 template <int D, int BASE, int s, int NBLK = 1>
 __device__ __forceinline__ void radix_dif_stage(uint64_t (&v)[16]) {
@@ -113,39 +116,49 @@ __device__ __forceinline__ void radix_dif_stage(uint64_t (&v)[16]) {
     // shift twiddles of the stage the same way. A stage of a radix-16 butterfly has three or four branches instead of twenty-four.
 #if RARE_STAGE_COMBINED
     // ONE group per stage: the butterflies and then the shift twiddles of their differences, all fast paths back to back. A
-    // difference whose second borrow is pending (true d = d_fast - e) goes through its shift as it is: the shift is linear and exact
-    // for any representative, so the true result is shift(d_fast) - e 2^K, a compile-time constant to subtract in the flagged lanes.
+    // difference whose correction is pending (second borrow: true d = d_fast - e; missed carry: true d = d_fast + 2^32, gl_field.h sub_f)
+    // goes through its shift as it is: the shift is linear and exact for any representative, so the true result is shift(d_fast) - e 2^K
+    // or shift(d_fast) + 2^(32 + K), compile-time constants to apply in the flagged lanes (gl::sub_fix_shifted).
     if constexpr (s > 0 && NB <= 8) {
-        gl::rare_mask fa[NB], fs[NB], fm[NB];
-        static_for<0, NB>([&](auto B_) {
-            constexpr int b = decltype(B_)::value, bb = b % NBP;
-            constexpr int i0 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half), i1 = i0 + half;
-            constexpr int K = (39 * (bb % half) * (32 >> s)) % 192;
-            gl::bfly_f<(K >= 96)>(v[i0], v[i1], v[i0], v[i1], fa[b], fs[b]);
-        });
-        static_for<0, NB>([&](auto B_) {
-            constexpr int b = decltype(B_)::value, bb = b % NBP;
-            constexpr int i1 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half) + half;
-            constexpr int K = (39 * (bb % half) * (32 >> s)) % 192, KK = K >= 96 ? K - 96 : K;
-            v[i1] = gl::mul_pow2_f<KK>(v[i1], fm[b]);
-        });
-        __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);
-        gl::rare_mask any = 0;
-        static_for<0, NB>([&](auto B_) { constexpr int b = decltype(B_)::value; any |= fa[b] | fs[b] | fm[b]; });
-        if (GL_RARE_ANY(any)) {
-            static_for<0, NB>([&](auto B_) {
-                constexpr int b = decltype(B_)::value, bb = b % NBP;
+        // The four-instruction subtraction hands out two masks (gl_field.h): with the sum's and the shift's that is up to four scalar
+        // pairs per butterfly, and the masks of a group stay live until its branch. RARE_STAGE_CHUNK butterflies form a group, so that
+        // a group's masks fit the scalar registers the passes have to spare (no scalar spills into vector lanes).
+        constexpr int CH = NB < RARE_STAGE_CHUNK ? NB : RARE_STAGE_CHUNK;
+        static_for<0, (NB + CH - 1) / CH>([&](auto C_) {
+            constexpr int c0 = decltype(C_)::value * CH, CN = NB - c0 < CH ? NB - c0 : CH;
+            gl::rare_mask fa[CN], fs[CN], fl[CN], fm[CN];
+            static_for<0, CN>([&](auto B_) {
+                constexpr int k = decltype(B_)::value, b = c0 + k, bb = b % NBP;
                 constexpr int i0 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half), i1 = i0 + half;
-                constexpr int K = (39 * (bb % half) * (32 >> s)) % 192, KK = K >= 96 ? K - 96 : K;
-                v[i0] = gl::add_fix(v[i0], fa[b]);
-                v[i1] = gl::mul_pow2_fix<KK>(v[i1], fm[b]);
-                #ifdef RARE_STAGE_WRONG_CONSTANT   // negative control of the tests only: the build must FAIL tests/test_gpu_ntt.py's rare-path test
-                v[i1] = gl::sub(v[i1], gl::masked_const<gl::eps_times_pow2(KK) + 1>(fs[b]));
-#else
-                v[i1] = gl::sub(v[i1], gl::masked_const<gl::eps_times_pow2(KK)>(fs[b]));   // KK = 0: e itself
-#endif
+                constexpr int K = (39 * (bb % half) * (32 >> s)) % 192;
+                gl::bfly_f<(K >= 96)>(v[i0], v[i1], v[i0], v[i1], fa[k], fs[k], fl[k]);
             });
-        }
+            static_for<0, CN>([&](auto B_) {
+                constexpr int k = decltype(B_)::value, b = c0 + k, bb = b % NBP;
+                constexpr int i1 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half) + half;
+                constexpr int K = (39 * (bb % half) * (32 >> s)) % 192, KK = K >= 96 ? K - 96 : K;
+                v[i1] = gl::mul_pow2_f<KK>(v[i1], fm[k]);
+            });
+            __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);
+            gl::rare_mask any = 0;
+            static_for<0, CN>([&](auto B_) { constexpr int k = decltype(B_)::value; any |= fa[k] | fs[k] | fl[k] | fm[k]; });
+            if (GL_RARE_ANY(any)) {
+                static_for<0, CN>([&](auto B_) {
+                    constexpr int k = decltype(B_)::value, b = c0 + k, bb = b % NBP;
+                    constexpr int i0 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half), i1 = i0 + half;
+                    constexpr int K = (39 * (bb % half) * (32 >> s)) % 192, KK = K >= 96 ? K - 96 : K;
+                    v[i0] = gl::add_fix(v[i0], fa[k]);
+                    v[i1] = gl::mul_pow2_fix<KK>(v[i1], fm[k]);
+#if defined(RARE_STAGE_WRONG_CONSTANT)   // negative control of the tests only: the build must FAIL tests/test_gpu_ntt.py's rare-path test
+                    v[i1] = gl::sub_fix_shifted<KK, 1>(v[i1], fs[k], fl[k]);
+#elif defined(RARE_STAGE_WRONG_CARRY_CONSTANT)   // the same for the missed carry's constant: must FAIL tests/test_gpu_field_sub4.py's radix test
+                    v[i1] = gl::sub_fix_shifted<KK, 0, 1>(v[i1], fs[k], fl[k]);
+#else
+                    v[i1] = gl::sub_fix_shifted<KK>(v[i1], fs[k], fl[k]);   // KK = 0: e and 2^32 themselves
+#endif
+                });
+            }
+        });
         return;
     }
 #endif
@@ -153,23 +166,23 @@ __device__ __forceinline__ void radix_dif_stage(uint64_t (&v)[16]) {
     static_assert(NB % GB == 0, "whole groups");
     static_for<0, NB / GB>([&](auto G_) {
         constexpr int g0 = decltype(G_)::value * GB;
-        gl::rare_mask fa[GB], fs[GB];
+        gl::rare_mask fa[GB], fs[GB], fl[GB];
         static_for<0, GB>([&](auto B_) {
             constexpr int b = g0 + decltype(B_)::value, k = decltype(B_)::value, bb = b % NBP;
             constexpr int i0 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half), i1 = i0 + half;
             constexpr int K = (39 * (bb % half) * (32 >> s)) % 192;
             // 2^96 = -1: a twiddle 2^K with K >= 96 is -(2^(K-96)); the sign is absorbed by swapping the operands of the subtraction
-            gl::bfly_f<(K >= 96)>(v[i0], v[i1], v[i0], v[i1], fa[k], fs[k]);
+            gl::bfly_f<(K >= 96)>(v[i0], v[i1], v[i0], v[i1], fa[k], fs[k], fl[k]);
         });
         __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);  // the ORs behind the last operation, see rare_group
         gl::rare_mask any = 0;
-        static_for<0, GB>([&](auto B_) { any |= fa[decltype(B_)::value] | fs[decltype(B_)::value]; });
+        static_for<0, GB>([&](auto B_) { any |= fa[decltype(B_)::value] | fs[decltype(B_)::value] | fl[decltype(B_)::value]; });
         if (GL_RARE_ANY(any)) {
             static_for<0, GB>([&](auto B_) {
                 constexpr int b = g0 + decltype(B_)::value, k = decltype(B_)::value, bb = b % NBP;
                 constexpr int i0 = BASE + (b / NBP) * (1 << D) + (bb / half) * 2 * half + (bb % half), i1 = i0 + half;
                 v[i0] = gl::add_fix(v[i0], fa[k]);
-                v[i1] = gl::sub_fix(v[i1], fs[k]);
+                v[i1] = gl::sub_fix(v[i1], fs[k], fl[k]);
             });
         }
     });
@@ -271,72 +284,77 @@ __device__ __forceinline__ void shift_twiddles_radix4(uint64_t (&v)[16]) {
             });
     }
     // butterfly (a, c) -> (a + C, a - C) in slots (i0, i1), C = -c when CNEG: then slot i0 takes the difference and i1 the sum.
-    // f0 / f1: the masks of the values written to i0 / i1
-    auto bfly = [&](auto CNEG_, auto I0_, auto I1_, gl::rare_mask &f0, gl::rare_mask &f1) {
+    // f0 / f1: the masks of the values written to i0 / i1; fl: the missed-carry mask of the difference, whichever slot took it
+    auto bfly = [&](auto CNEG_, auto I0_, auto I1_, gl::rare_mask &f0, gl::rare_mask &f1, gl::rare_mask &fl) {
         constexpr bool cneg = decltype(CNEG_)::value;
         constexpr int i0 = decltype(I0_)::value, i1 = decltype(I1_)::value;
-        if constexpr (cneg) gl::bfly_f<false>(v[i0], v[i1], v[i1], v[i0], f1, f0);
-        else gl::bfly_f<false>(v[i0], v[i1], v[i0], v[i1], f0, f1);
+        if constexpr (cneg) gl::bfly_f<false>(v[i0], v[i1], v[i1], v[i0], f1, f0, fl);
+        else gl::bfly_f<false>(v[i0], v[i1], v[i0], v[i1], f0, f1, fl);
     };
     // correction of slot I: it holds a sum (IS_SUM) or a difference, and went through a shift by SHIFT afterwards (0: none)
-    auto fix = [&](auto IS_SUM_, auto SHIFT_, auto I_, gl::rare_mask f, gl::rare_mask fshift) {
+    // (fl: the pair's missed-carry mask, looked at only where the slot holds the difference)
+    auto fix = [&](auto IS_SUM_, auto SHIFT_, auto I_, gl::rare_mask f, gl::rare_mask fl, gl::rare_mask fshift) {
         constexpr bool is_sum = decltype(IS_SUM_)::value;
         constexpr int shift = decltype(SHIFT_)::value, i = decltype(I_)::value;
         if constexpr (shift == 0) {
-            v[i] = is_sum ? gl::add_fix(v[i], f) : gl::sub_fix(v[i], f);
+            v[i] = is_sum ? gl::add_fix(v[i], f) : gl::sub_fix(v[i], f, fl);
         } else {
             v[i] = gl::mul_pow2_fix<shift>(v[i], fshift);
-            const uint64_t c = gl::masked_const<gl::eps_times_pow2(shift)>(f);
-            v[i] = is_sum ? gl::add(v[i], c) : gl::sub(v[i], c);
+            if constexpr (is_sum) v[i] = gl::add(v[i], gl::masked_const<gl::eps_times_pow2(shift)>(f));
+            else v[i] = gl::sub_fix_shifted<shift>(v[i], f, fl);
         }
     };
     using std::integral_constant;
     using std::bool_constant;
-    {   // first stage: pairs (0, 2) and (1, 3) of every block, then 2^48 on slot 3
-        gl::rare_mask f0[8], f1[8], fm[4];
-        static_for<0, 4>([&](auto B_) {
-            constexpr int kblo = decltype(B_)::value, b = 4 * kblo;
-            bfly(bool_constant<NEGQ(kblo, 2)>{}, integral_constant<int, b>{}, integral_constant<int, b + 2>{}, f0[2 * kblo], f1[2 * kblo]);
-            bfly(bool_constant<NEGQ(kblo, 1) != NEGQ(kblo, 3)>{}, integral_constant<int, b + 1>{}, integral_constant<int, b + 3>{}, f0[2 * kblo + 1], f1[2 * kblo + 1]);
+    // Each stage in two groups of two blocks: with the three masks of a butterfly (sum, second borrow, missed carry) all four blocks
+    // together would hold 24 to 28 scalar pairs until the branch, more than the row pass has to spare.
+    static_for<0, 2>([&](auto H_) {   // first stage: pairs (0, 2) and (1, 3) of every block, then 2^48 on slot 3
+        constexpr int k0 = 2 * decltype(H_)::value;
+        gl::rare_mask f0[4], f1[4], fl[4], fm[2];
+        static_for<0, 2>([&](auto B_) {
+            constexpr int kk = decltype(B_)::value, kblo = k0 + kk, b = 4 * kblo;
+            bfly(bool_constant<NEGQ(kblo, 2)>{}, integral_constant<int, b>{}, integral_constant<int, b + 2>{}, f0[2 * kk], f1[2 * kk], fl[2 * kk]);
+            bfly(bool_constant<NEGQ(kblo, 1) != NEGQ(kblo, 3)>{}, integral_constant<int, b + 1>{}, integral_constant<int, b + 3>{}, f0[2 * kk + 1], f1[2 * kk + 1], fl[2 * kk + 1]);
         });
-        static_for<0, 4>([&](auto B_) {
-            constexpr int kblo = decltype(B_)::value;
-            v[4 * kblo + 3] = gl::mul_pow2_f<48>(v[4 * kblo + 3], fm[kblo]);
+        static_for<0, 2>([&](auto B_) {
+            constexpr int kk = decltype(B_)::value, kblo = k0 + kk;
+            v[4 * kblo + 3] = gl::mul_pow2_f<48>(v[4 * kblo + 3], fm[kk]);
         });
         __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);
         gl::rare_mask any = 0;
-        static_for<0, 8>([&](auto I_) { any |= f0[decltype(I_)::value] | f1[decltype(I_)::value]; });
-        static_for<0, 4>([&](auto I_) { any |= fm[decltype(I_)::value]; });
+        static_for<0, 4>([&](auto I_) { any |= f0[decltype(I_)::value] | f1[decltype(I_)::value] | fl[decltype(I_)::value]; });
+        static_for<0, 2>([&](auto I_) { any |= fm[decltype(I_)::value]; });
         if (GL_RARE_ANY(any))
-            static_for<0, 4>([&](auto B_) {
-                constexpr int kblo = decltype(B_)::value, b = 4 * kblo;
+            static_for<0, 2>([&](auto B_) {
+                constexpr int kk = decltype(B_)::value, kblo = k0 + kk, b = 4 * kblo;
                 constexpr bool na = NEGQ(kblo, 2), nb = NEGQ(kblo, 1) != NEGQ(kblo, 3);
-                fix(bool_constant<!na>{}, integral_constant<int, 0>{}, integral_constant<int, b>{}, f0[2 * kblo], 0);
-                fix(bool_constant<na>{}, integral_constant<int, 0>{}, integral_constant<int, b + 2>{}, f1[2 * kblo], 0);
-                fix(bool_constant<!nb>{}, integral_constant<int, 0>{}, integral_constant<int, b + 1>{}, f0[2 * kblo + 1], 0);
-                fix(bool_constant<nb>{}, integral_constant<int, 48>{}, integral_constant<int, b + 3>{}, f1[2 * kblo + 1], fm[kblo]);
+                fix(bool_constant<!na>{}, integral_constant<int, 0>{}, integral_constant<int, b>{}, f0[2 * kk], fl[2 * kk], 0);
+                fix(bool_constant<na>{}, integral_constant<int, 0>{}, integral_constant<int, b + 2>{}, f1[2 * kk], fl[2 * kk], 0);
+                fix(bool_constant<!nb>{}, integral_constant<int, 0>{}, integral_constant<int, b + 1>{}, f0[2 * kk + 1], fl[2 * kk + 1], 0);
+                fix(bool_constant<nb>{}, integral_constant<int, 48>{}, integral_constant<int, b + 3>{}, f1[2 * kk + 1], fl[2 * kk + 1], fm[kk]);
             });
-    }
-    {   // second stage: pairs (0, 1) and (2, 3); their subtrahends carry the sign of x1
-        gl::rare_mask f0[8], f1[8];
-        static_for<0, 4>([&](auto B_) {
-            constexpr int kblo = decltype(B_)::value, b = 4 * kblo;
-            bfly(bool_constant<NEGQ(kblo, 1)>{}, integral_constant<int, b>{}, integral_constant<int, b + 1>{}, f0[2 * kblo], f1[2 * kblo]);
-            bfly(bool_constant<NEGQ(kblo, 1)>{}, integral_constant<int, b + 2>{}, integral_constant<int, b + 3>{}, f0[2 * kblo + 1], f1[2 * kblo + 1]);
+    });
+    static_for<0, 2>([&](auto H_) {   // second stage: pairs (0, 1) and (2, 3); their subtrahends carry the sign of x1
+        constexpr int k0 = 2 * decltype(H_)::value;
+        gl::rare_mask f0[4], f1[4], fl[4];
+        static_for<0, 2>([&](auto B_) {
+            constexpr int kk = decltype(B_)::value, kblo = k0 + kk, b = 4 * kblo;
+            bfly(bool_constant<NEGQ(kblo, 1)>{}, integral_constant<int, b>{}, integral_constant<int, b + 1>{}, f0[2 * kk], f1[2 * kk], fl[2 * kk]);
+            bfly(bool_constant<NEGQ(kblo, 1)>{}, integral_constant<int, b + 2>{}, integral_constant<int, b + 3>{}, f0[2 * kk + 1], f1[2 * kk + 1], fl[2 * kk + 1]);
         });
         __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);
         gl::rare_mask any = 0;
-        static_for<0, 8>([&](auto I_) { any |= f0[decltype(I_)::value] | f1[decltype(I_)::value]; });
+        static_for<0, 4>([&](auto I_) { any |= f0[decltype(I_)::value] | f1[decltype(I_)::value] | fl[decltype(I_)::value]; });
         if (GL_RARE_ANY(any))
-            static_for<0, 4>([&](auto B_) {
-                constexpr int kblo = decltype(B_)::value, b = 4 * kblo;
+            static_for<0, 2>([&](auto B_) {
+                constexpr int kk = decltype(B_)::value, kblo = k0 + kk, b = 4 * kblo;
                 constexpr bool n1 = NEGQ(kblo, 1);
-                fix(bool_constant<!n1>{}, integral_constant<int, 0>{}, integral_constant<int, b>{}, f0[2 * kblo], 0);
-                fix(bool_constant<n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 1>{}, f1[2 * kblo], 0);
-                fix(bool_constant<!n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 2>{}, f0[2 * kblo + 1], 0);
-                fix(bool_constant<n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 3>{}, f1[2 * kblo + 1], 0);
+                fix(bool_constant<!n1>{}, integral_constant<int, 0>{}, integral_constant<int, b>{}, f0[2 * kk], fl[2 * kk], 0);
+                fix(bool_constant<n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 1>{}, f1[2 * kk], fl[2 * kk], 0);
+                fix(bool_constant<!n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 2>{}, f0[2 * kk + 1], fl[2 * kk + 1], 0);
+                fix(bool_constant<n1>{}, integral_constant<int, 0>{}, integral_constant<int, b + 3>{}, f1[2 * kk + 1], fl[2 * kk + 1], 0);
             });
-    }
+    });
 }
 
 // Synchronisation of the NT_ threads that share a tile: a wavefront (NT_ == 64) needs only program order.

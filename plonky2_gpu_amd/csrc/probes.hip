@@ -25,12 +25,25 @@ __device__ uint64_t pow2_case(uint64_t x, int k) {
 template <int KIND>
 __device__ uint64_t deferred_group(uint64_t x, uint64_t y, int which) {
     uint64_t a[3] = {x, y, x ^ y}, b[3] = {y, x, x}, r[3];
+    gl::rare_mask f[3], fl[3] = {0, 0, 0};   // fl: sub_f's second mask (the missed carry)
+#pragma unroll
+    for (int k = 0; k < 3; k++) r[k] = KIND == 0 ? gl::add_f(a[k], b[k], f[k]) : KIND == 1 ? gl::sub_f(a[k], b[k], f[k], fl[k]) : gl::mul_f(a[k], b[k], f[k]);
+    if (GL_RARE_ANY(f[0] | f[1] | f[2] | fl[0] | fl[1] | fl[2])) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) r[k] = KIND == 0 ? gl::add_fix(r[k], f[k]) : KIND == 1 ? gl::sub_fix(r[k], f[k], fl[k]) : gl::mul_fix(r[k], f[k]);
+    }
+    return which == 0 ? r[0] : which == 1 ? r[1] : r[2];
+}
+// canon_f / canon_fix the way the passes' tails use them: x, y and x ^ y flagged by one compare each, one branch, the exact
+// conditional subtraction behind it; `which` as above. The kernel's own gl::canon of the result must then change nothing.
+__device__ uint64_t canon_group(uint64_t x, uint64_t y, int which) {
+    uint64_t r[3] = {x, y, x ^ y};
     gl::rare_mask f[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) r[k] = KIND == 0 ? gl::add_f(a[k], b[k], f[k]) : KIND == 1 ? gl::sub_f(a[k], b[k], f[k]) : gl::mul_f(a[k], b[k], f[k]);
+    for (int k = 0; k < 3; k++) gl::canon_f(r[k], f[k]);
     if (GL_RARE_ANY(f[0] | f[1] | f[2])) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) r[k] = KIND == 0 ? gl::add_fix(r[k], f[k]) : KIND == 1 ? gl::sub_fix(r[k], f[k]) : gl::mul_fix(r[k], f[k]);
+        for (int k = 0; k < 3; k++) r[k] = gl::canon_fix(r[k], f[k]);
     }
     return which == 0 ? r[0] : which == 1 ? r[1] : r[2];
 }
@@ -117,9 +130,10 @@ __global__ void field_op_kernel(int op, const uint64_t *a, const uint64_t *b, ui
         case 21: case 22: case 23: r = deferred_group<1>(x, y, op - 21); break;
         case 24: case 25: case 26: r = deferred_group<2>(x, y, op - 24); break;
         case 27: r = pow2f_case<0>(x, (int)((uint32_t)y % 96), (y >> 32) != 0); break;
+        case 28: case 29: case 30: r = canon_group(x, y, op - 28); break;
         default: r = x; break;
     }
-    out[i] = (op >= 8 && op <= 12) ? r : gl::canon(r);  // canonical-domain ops must already be canonical
+    out[i] = ((op >= 8 && op <= 12) || (op >= 28 && op <= 30)) ? r : gl::canon(r);  // canonical-domain ops (and canon_fix) must already be canonical
 }
 
 }  // namespace

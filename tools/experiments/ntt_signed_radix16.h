@@ -27,11 +27,11 @@ __device__ __forceinline__ void radix16_stage_signed(uint64_t (&v)[16]) {
     constexpr auto I0 = [](int bb) { return (bb / half) * 2 * half + (bb % half); };
     constexpr auto KOF = [](int bb) { return (39 * (bb % half) * (32 >> s)) % 192; };
     constexpr auto TAU = [](int bb) { return (((SG >> ((bb / half) * 2 * half + (bb % half))) ^ (SG >> ((bb / half) * 2 * half + (bb % half) + half))) & 1u) != 0; };
-    gl::rare_mask f0[8], f1[8], fm[8];   // f0 / f1: masks of the values written to slots i0 / i1; fm: of the shift
+    gl::rare_mask f0[8], f1[8], fl[8], fm[8];   // f0 / f1: masks of the values written to slots i0 / i1; fl: the difference's missed carry; fm: of the shift
     static_for<0, 8>([&](auto B_) {
         constexpr int bb = decltype(B_)::value, i0 = I0(bb), i1 = i0 + half;
-        if constexpr (TAU(bb)) gl::bfly_f<false>(v[i0], v[i1], v[i1], v[i0], f1[bb], f0[bb]);        // i0 <- a - c, i1 <- a + c
-        else gl::bfly_f<(KOF(bb) >= 96)>(v[i0], v[i1], v[i0], v[i1], f0[bb], f1[bb]);                // i0 <- a + c, i1 <- +-(a - c)
+        if constexpr (TAU(bb)) gl::bfly_f<false>(v[i0], v[i1], v[i1], v[i0], f1[bb], f0[bb], fl[bb]);        // i0 <- a - c, i1 <- a + c
+        else gl::bfly_f<(KOF(bb) >= 96)>(v[i0], v[i1], v[i0], v[i1], f0[bb], f1[bb], fl[bb]);                // i0 <- a + c, i1 <- +-(a - c)
     });
     static_for<0, 8>([&](auto B_) {
         constexpr int bb = decltype(B_)::value, i1 = I0(bb) + half, KK = KOF(bb) % 96;
@@ -39,14 +39,15 @@ __device__ __forceinline__ void radix16_stage_signed(uint64_t (&v)[16]) {
     });
     __builtin_amdgcn_sched_barrier(RARE_FENCE_MASK);
     gl::rare_mask any = 0;
-    static_for<0, 8>([&](auto B_) { constexpr int bb = decltype(B_)::value; any |= f0[bb] | f1[bb] | fm[bb]; });
+    static_for<0, 8>([&](auto B_) { constexpr int bb = decltype(B_)::value; any |= f0[bb] | f1[bb] | fl[bb] | fm[bb]; });
     if (GL_RARE_ANY(any))
         static_for<0, 8>([&](auto B_) {
             constexpr int bb = decltype(B_)::value, i0 = I0(bb), i1 = i0 + half, KK = KOF(bb) % 96;
-            v[i0] = TAU(bb) ? gl::sub_fix(v[i0], f0[bb]) : gl::add_fix(v[i0], f0[bb]);
+            v[i0] = TAU(bb) ? gl::sub_fix(v[i0], f0[bb], fl[bb]) : gl::add_fix(v[i0], f0[bb]);
             v[i1] = gl::mul_pow2_fix<KK>(v[i1], fm[bb]);
-            const uint64_t c = gl::masked_const<gl::eps_times_pow2(KK)>(f1[bb]);   // the pending e of the sum / difference, through the shift
-            v[i1] = TAU(bb) ? gl::add(v[i1], c) : gl::sub(v[i1], c);
+            // the pending correction of the sum / difference, through the shift
+            if constexpr (TAU(bb)) v[i1] = gl::add(v[i1], gl::masked_const<gl::eps_times_pow2(KK)>(f1[bb]));
+            else v[i1] = gl::sub_fix_shifted<KK>(v[i1], f1[bb], fl[bb]);
         });
 }
 // v[w] *= 2^(UNIT KB w) (w = 1 .. 15: the twiddle w_16G^(KB w) of the column pass, UNIT = 39 * 4 / G), then the radix 16 over w
