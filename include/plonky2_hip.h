@@ -1030,6 +1030,81 @@ GlError gl_debug_keccak_sponge_table_stage_ms(const uint64_t *d_ops, uint64_t nu
                                               uint64_t *d_trace, uint64_t trace_stride, void *d_scratch, float *h_ms, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The arithmetic table: the reference's ArithmeticStark (evm/src/arithmetic/), 92 columns — the table of the EVM's 256-bit ADD, MUL,
+ * SUB, LT, GT (one row each) and DIV, MOD, ADDMOD, SUBMOD, MULMOD (two rows each) — with its trace built in HBM from a compact
+ * operation list and its constraints emitted natively, so that gl_stark_prove / gl_stark_tables_prove prove it without the trace
+ * ever visiting the host. The reference's snapshot has the columns, ArithmeticStark::generate(lv, nv) for ONE operation's derived
+ * cells and eval_packed_generic; it has no generate_trace, no range check and no cross-table lookup, the table is not in AllStark,
+ * and generate panics on SHL and SHR. The TABLE is therefore defined here; the cells of an operation are bit for bit what
+ * add / sub / mul / compare / modular::generate write.
+ * d_ops: [num_ops][25] words of 64 bits in device memory, one record per operation: word 0 the operator, given as the index of its
+ * flag column (ADD 0, MUL 1, SUB 2, DIV 3, MOD 4, ADDMOD 5, SUBMOD 6, MULMOD 7, LT 8, GT 9); words 1 .. 8, 9 .. 16 and 17 .. 24 the
+ * eight 32-bit limbs of in0, in1 and in2, least significant first. ADD, MUL, SUB, LT, GT take (in0, in1) and in2 must be zero;
+ * ADDMOD, SUBMOD, MULMOD take in2 as the modulus; MOD and DIV take in0 as numerator and in2 as denominator, and in1 must be zero.
+ * The results are not part of the record: the device computes them. LIMITS, checked on the device: the operator is 0 .. 9 (SHL 10
+ * and SHR 11 have flag columns that are always zero here), every limb is below 2^32, the must-be-zero input is zero;
+ * num_ops <= 2^22.
+ * d_trace receives [92][pitch trace_stride] value columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. Columns
+ * (columns.rs:25-117): the flags IS_ADD .. IS_SHR 0 .. 11, then five ranges of sixteen 16-bit limbs, least significant first:
+ * GENERAL_INPUT_0 12 .. 27 (in0), GENERAL_INPUT_1 28 .. 43 (in1), GENERAL_INPUT_2 44 .. 59, GENERAL_INPUT_3 60 .. 75,
+ * AUX_INPUT_0_LO 76 .. 91. ADD, SUB: the result in 44 .. 59. MUL: the result in 44 .. 59, mul.rs' aux carries in 60 .. 75. LT, GT:
+ * the result in column 44 (45 .. 59 zero), the difference in 60 .. 75. Modular operations, first row: the modulus AS GIVEN in
+ * 44 .. 59 (zero stays zero; the substitution by 1, or by 2^256 for DIV, is local to the witness, as in generate_modular_op), the
+ * output (the remainder) in 60 .. 75, the low sixteen quotient limbs in 76 .. 91 — DIV's result; second row: all twelve flags
+ * zero, MODULAR_QUO_INPUT_HI 12 .. 27 (the high sixteen quotient limbs), MODULAR_AUX_INPUT 28 .. 58 (31 values),
+ * MODULAR_MOD_IS_ZERO 59, MODULAR_OUT_AUX_RED 60 .. 75, 76 .. 91 zero. Every shared cell of a one-row operation that the
+ * reference does not write is zero. Signed values (the quotient limbs of a SUBMOD with in0 < in1, the aux values) are stored
+ * canonically, p - |v|. A zero modulus or denominator gives the result 0.
+ * ROWS: the operations stand in list order; operation k starts at the exclusive prefix sum of the row counts; the rows behind the
+ * operations are all zero. Every flag constraint is filtered, so second rows and padding satisfy the program. rows = the sum of
+ * the row counts depends on the data and is returned in *h_rows; d_trace == NULL asks for the count alone (trace_stride is not
+ * read). rows > n is REFUSED and the message names the count needed; a modular operation whose second row is row n - 1 is allowed.
+ * Every word of the 92 columns is written on all n rows and is canonical: the buffer need not be zeroed; the words between n and
+ * trace_stride are left untouched. num_ops == 0 is allowed (d_ops may then be NULL) and gives an all-padding trace.
+ * PROTOCOL, as gl_keccak_sponge_table_trace's: validation, the per-operation row counts and their exclusive prefix sums run on
+ * ctx->stream; the host then reads the row count and the status words — the call's ONE host wait —; the fill is enqueued behind
+ * it and the call returns without waiting for it. With num_ops == 0 nothing is counted and the call does not wait. The fill is
+ * one lane per operation (a 512-by-256-bit division with fixed trip counts for the modular operators; nothing goes to scratch
+ * memory) and one lane per zero row. Nothing is allocated: d_scratch is gl_arithmetic_table_scratch_bytes(num_ops, degree_bits)
+ * bytes in device memory, 16-byte aligned (32 + 8 num_ops bytes and a little), and holds nothing between calls; 0 is returned for
+ * arguments out of range.
+ * Refused with GL_E_INVALID and a message that names the reason, the trace untouched — for the data: a record outside the limits
+ * (the message names the LOWEST record at fault and its fault — the operator, else a limb, else the must-be-zero input —;
+ * *h_rows is 0); rows > n (*h_rows says what is needed) — and before anything is launched: a NULL pointer other than d_trace and
+ * (with num_ops == 0) d_ops, num_ops > 2^22, degree_bits outside 1 ..= 22 (what gl_stark_create takes for constraints of degree
+ * 5), d_scratch not 16-byte aligned, trace_stride < n, d_ops, d_trace and d_scratch overlapping one another.
+ * gl_arithmetic_table_program = arithmetic_stark.rs:72-87 as ONE STARK program in the encoding of GlStarkDesc.h_instrs, 246
+ * constraints in the reference's order (the order decides the powers of alpha and so the proof's bytes): add 16, sub 16, mul 16,
+ * compare 35 (the bit check, then 17 for LT and 17 for GT), modular 163 — constraint_last_row of the five modular flags' sum, the
+ * two mod_is_zero checks, 16 + 1 of the less-than that shows the output reduced, the 15 high coefficients of quot * modulus, and
+ * 4 x 32 coefficients of c + q m + (x - 2^16) s against the inputs of ADDMOD, SUBMOD, MULMOD and MOD / DIV —; everything in
+ * modular behind the last-row check is a transition constraint. Product coefficients are formed on demand from LOAD_WIRE /
+ * LOAD_NEXT; 2^16 and 2^-16 are immediates; the program stays within 64 registers and uses no accumulator. Device-free; the
+ * result is laid out and released as gl_keccak_table_program's. No public inputs, no permutation pairs.
+ * CONSTRAINT DEGREE: the reference's constraint_degree() says 3, but modular.rs:350 adds mod_is_zero * lv[IS_DIV] to limb 0 of
+ * the output and the less-than then yields filter * t * (2^16 - t) with that quadratic t: sixteen constraints of degree 5
+ * wherever the IS_DIV column and column 59 are not zero polynomials. A proof at declared degree 3 of such a trace is refused by
+ * the verifier at zeta (tests/test_arithmetic_table_ref.py). Declare constraint_degree 5 (quotient_degree_factor 4, rate_bits >=
+ * 2) for any trace that may hold a DIV row; 3 is sound only for a trace without one.
+ * CROSS-TABLE LOOKUPS: the reference has none for this table. The result sits in a different range per operator family, so three
+ * looked entries are offered, each over an operation's first row, values as eight 32-bit limbs lo + 2^16 hi of adjacent 16-bit
+ * columns: "binary" — the flags 0, 1, 2, 8, 9, in0, in1, columns 44 .. 59, filter the sum of those flags; "modular" — the flags
+ * 4, 5, 6, 7, in0, in1, in2, columns 60 .. 75, filter their sum; "div" — in0, in2, columns 76 .. 91, filter IS_DIV.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_ARITHMETIC_TABLE_COLUMNS 92
+#define GL_ARITHMETIC_TABLE_OP_WORDS 25
+uint64_t gl_arithmetic_table_scratch_bytes(uint64_t num_ops, uint32_t degree_bits);
+GlError gl_arithmetic_table_trace(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                                  void *d_scratch, uint64_t *h_rows, void *ctx);
+GlError gl_arithmetic_table_program(GlGatePrograms *out);
+/* Measurement hook: gl_arithmetic_table_trace with an event between its stages. h_ms[2] receives the milliseconds of the counting
+ * pass and of the fill; the host's wait for the count lies between them and belongs to neither. d_trace and num_ops >= 1 are
+ * required. Creates and destroys its events and waits for ctx->stream before it returns: not for use next to a proof in flight on
+ * the same context. */
+GlError gl_debug_arithmetic_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                                           uint64_t trace_stride, void *d_scratch, float *h_ms, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

@@ -521,6 +521,29 @@ inline KeccakSpongeTableProgram keccak_sponge_table_program() {
     return out;
 }
 
+// The arithmetic table (plonky2_hip.h "The arithmetic table"). arithmetic_table_trace: d_ops [num_ops][25] records (operator, the
+// limbs of in0, in1, in2) -> d_trace [92][trace_stride] with 2^degree_bits rows; returns the rows the operations take, which is
+// all a call with d_trace == nullptr computes. d_scratch: gl_arithmetic_table_scratch_bytes(num_ops, degree_bits) bytes in HBM.
+// The call waits once, for the count. arithmetic_table_program: its constraints (declare constraint_degree 5 where a DIV row may
+// exist; no public inputs, no pairs).
+inline uint64_t arithmetic_table_trace(const Context &ctx, const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                                       uint64_t trace_stride, void *d_scratch) {
+    uint64_t rows = 0;
+    check(gl_arithmetic_table_trace(d_ops, num_ops, degree_bits, d_trace, trace_stride, d_scratch, &rows, ctx.get()));
+    return rows;
+}
+using ArithmeticTableProgram = KeccakTableProgram;  // instructions, immediates and the number of constraints
+inline ArithmeticTableProgram arithmetic_table_program() {
+    GlGatePrograms p;
+    check(gl_arithmetic_table_program(&p));
+    ArithmeticTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 // gl_stark_split_program: the unit programs gl_stark_compile_units cuts desc's program into (device-free). Every unit is a
 // program of its own over desc's immediates; its EMITs are numbers emit_start .. emit_end - 1 of the program's.
 struct StarkProgramUnit {
