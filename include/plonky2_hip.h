@@ -133,7 +133,8 @@ void gl_event_destroy(void *event);
  * log_n <= 24. stride >= 2^log_n; for inverse, stride must be a multiple of 2^log_n. The passes move 16 bytes at a time:
  * d_values must be 16-byte aligned and, when poly_num > 1 and log_n > 0, stride even (one polynomial has no stride: any
  * value >= 2^log_n is accepted). Words between the polynomials (stride > 2^log_n) are not written. A violation is
- * GL_E_INVALID and nothing is touched. */
+ * GL_E_INVALID and nothing is touched. Here and in every call that takes a stride or a pitch, it has no upper bound: every
+ * offset `column * stride` is formed in 64 bits, so columns may lie more than 2^32 words apart. */
 GlError gl_ntt_batch(uint64_t *d_values, uint64_t poly_num, uint32_t log_n, uint64_t stride, int inverse,
                      int bit_reversed, void *ctx);
 

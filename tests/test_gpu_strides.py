@@ -22,6 +22,7 @@ Planner branch (product build)                                                  
               three passes (22, 23), contiguous and one call per polynomial        test_coset_lde_padded_strides[22-1|23-0]
               the 65535-polynomial step crossed                                    test_ntt_and_lde_batches_of_more_than_65535_polynomials
   the diagnostic build's kernel selections at a padded stride                      test_gpu_ntt.py::test_alternative_kernel_selections
+  every entry point that takes a pitch, the last column behind 2^32 words           test_gpu_far_pitch.py (layout: tests/far.py)
 
 NOT reachable: the 65535-polynomial step of the plans from 2^22 up (bit-reversed in place; the three-pass LDE): 65536 polynomials
 of 2^22 points are 2.2 TB. The step is crossed at 2^13 only. log_n = 0 moves single words and has no plan. The bit-reversed
