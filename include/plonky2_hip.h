@@ -1106,6 +1106,61 @@ GlError gl_debug_arithmetic_table_stage_ms(const uint64_t *d_ops, uint64_t num_o
                                            uint64_t trace_stride, void *d_scratch, float *h_ms, void *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * The Poseidon table: the permutation unit of the reference's system_zero crate (system_zero/src/permutation_unit.rs,
+ * system_zero/src/registers/permutation.rs with START_PERMUTATION = 0) as a table of its own — every cell a degree-3 constraint
+ * system needs for one width-12 Poseidon permutation over Goldilocks lies in one row — built on the device from a record list.
+ * gl_poseidon_table_trace = generate_permutation_unit (permutation_unit.rs:56-105) on every row.
+ * d_ops: [num_ops][13] words of 64 bits in device memory, one record per row. Word 0 is the kind:
+ *   0, START: words 1 .. 12 are the whole input state;
+ *   k = 1 .. 8, ABSORB: the row continues the sponge of the row before it — its input is that row's OUTPUT with elements
+ *   0 .. k - 1 overwritten by words 1 .. k (the overwrite mode of plonky2's hash_n_to_m_no_pad); words k + 1 .. 12 are ignored.
+ * Element words are any u64 and are reduced mod p; a kind word is compared as it stands. LIMITS, checked on the device: a kind is
+ * 0 .. 8, and record 0 is a START.
+ * d_trace receives [249][pitch trace_stride] value columns with n = 2^degree_bits rows, the layout gl_stark_prove takes. Columns:
+ * INPUT 0 .. 11, the state before round 0; first full rounds r = 0 .. 3: mid_sbox 12 + 24 r + i, after_mds 24 + 24 r + i;
+ * partial rounds r = 0 .. 21: mid_sbox 108 + 2 r, after_sbox 109 + 2 r; second full rounds r = 0 .. 3: mid_sbox 152 + 24 r + i,
+ * after_mds 164 + 24 r + i; OUTPUT 236 .. 247 is the second full rounds' last after_mds; IS_REAL 248. mid_sbox is the CUBE of
+ * the state behind the constant layer, after_mds the state behind the MDS layer and BEFORE the next round's constants,
+ * after_sbox element 0 to the seventh power. IS_REAL is not the reference's: its unit has no filter because nothing looks into
+ * it yet; it is 1 on a row a record made and 0 on padding.
+ * ROWS: the record order is the row order; the rows num_ops .. n - 1 are padding rows. A padding row is NOT a zero row — the
+ * constraints hold on every row —: it is the permutation of the all-zero state with IS_REAL = 0, the row the reference's
+ * generate_trace_rows writes everywhere. Every word of the 249 columns is written on all n rows and is canonical: the buffer need
+ * not be zeroed; the words between n and trace_stride are left untouched. num_ops == 0 is allowed (d_ops may then be NULL).
+ * PROTOCOL: the validation (one thread per record) runs on ctx->stream; the host reads its 16 bytes — the call's ONE host wait
+ * —; behind it, where the list holds an ABSORB, a serial pass (one lane per record: the lane of a START that an ABSORB follows
+ * walks its run and writes the INPUT words of the continuation rows; a run as long as the list runs on one lane), then the rows
+ * (one lane per row, all thirty rounds in registers) are enqueued and the call returns without waiting for them. With
+ * num_ops == 0 nothing is validated and the call does not wait. Nothing is allocated: d_scratch is
+ * GL_POSEIDON_TABLE_SCRATCH_BYTES bytes in device memory, 16-byte aligned, and holds nothing between calls.
+ * Refused with GL_E_INVALID and a message that names the reason, the trace untouched — for the data, with the LOWEST record at
+ * fault named: a kind above 8; record 0 being an ABSORB ("continues a sponge that no record starts") — and before anything is
+ * launched: a NULL pointer (d_ops only with num_ops > 0), degree_bits outside 1 ..= GL_POSEIDON_TABLE_MAX_DEGREE_BITS (what
+ * gl_stark_create takes for constraints of degree 3), num_ops > n, trace_stride < n, d_scratch not 16-byte aligned, d_ops,
+ * d_trace and d_scratch overlapping one another.
+ * gl_poseidon_table_program = eval_permutation_unit (permutation_unit.rs:108-172) as ONE STARK program in the encoding of
+ * GlStarkDesc.h_instrs, 236 constraints in the reference's order (the order decides the powers of alpha and so the proof's
+ * bytes), then IS_REAL (IS_REAL - 1): 237. The constant layers are LOAD_IMM + ADD, the MDS layers ACC / ACCR (a row's weights
+ * sum to 264); the program stays within 64 registers. Device-free; the result is laid out and released as
+ * gl_keccak_table_program's. Declare constraint_degree 3, no public inputs, no permutation pairs.
+ * CROSS-TABLE LOOKUPS: one looked entry, "permutation": the 12 INPUT and the 12 OUTPUT columns, filter IS_REAL.
+ * ------------------------------------------------------------------------------------------- */
+#define GL_POSEIDON_TABLE_COLUMNS 249
+#define GL_POSEIDON_TABLE_OP_WORDS 13
+#define GL_POSEIDON_TABLE_SCRATCH_BYTES 16
+#define GL_POSEIDON_TABLE_MAX_DEGREE_BITS 23
+GlError gl_poseidon_table_trace(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace, uint64_t trace_stride,
+                                void *d_scratch, void *ctx);
+GlError gl_poseidon_table_program(GlGatePrograms *out);
+/* Measurement hook: gl_poseidon_table_trace with an event between its stages and a choice of the rows kernel's MDS layer — mds 0:
+ * the product's, 1: on the matrix cores, 2: on the vector ALU; the three write the same trace. h_ms[3] receives the milliseconds
+ * of the validation, of the serial pass (negative: it did not run, the list holds no ABSORB) and of the rows; the host's wait for
+ * the status words lies behind the validation and belongs to no stage. num_ops >= 1 is required. Creates and destroys its events
+ * and waits for ctx->stream before it returns: not for use next to a proof in flight on the same context. */
+GlError gl_debug_poseidon_table_stage_ms(const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                                         uint64_t trace_stride, void *d_scratch, uint32_t mds, float *h_ms, void *ctx);
+
+/* ---------------------------------------------------------------------------------------------
  * (A) the reference's extern "C" surface (cuda/src/lib.rs:58-145). Synchronous.
  * ------------------------------------------------------------------------------------------- */
 

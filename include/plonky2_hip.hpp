@@ -544,6 +544,27 @@ inline ArithmeticTableProgram arithmetic_table_program() {
     return out;
 }
 
+// The Poseidon table (plonky2_hip.h "The Poseidon table"). poseidon_table_trace: d_ops [num_ops][13] records (the kind — 0 START,
+// k = 1 .. 8 ABSORB of k elements into the row before — and twelve element words, any u64) -> d_trace [249][trace_stride] with
+// 2^degree_bits rows, list order = row order, behind them the permutation of the all-zero state with IS_REAL = 0. d_scratch:
+// GL_POSEIDON_TABLE_SCRATCH_BYTES bytes in HBM, 16-byte aligned. The call waits once, for the validation (not at all with
+// num_ops == 0). poseidon_table_program: its constraints (constraint_degree 3, no public inputs, no pairs).
+inline void poseidon_table_trace(const Context &ctx, const uint64_t *d_ops, uint64_t num_ops, uint32_t degree_bits, uint64_t *d_trace,
+                                 uint64_t trace_stride, void *d_scratch) {
+    check(gl_poseidon_table_trace(d_ops, num_ops, degree_bits, d_trace, trace_stride, d_scratch, ctx.get()));
+}
+using PoseidonTableProgram = KeccakTableProgram;  // instructions, immediates and the number of constraints
+inline PoseidonTableProgram poseidon_table_program() {
+    GlGatePrograms p;
+    check(gl_poseidon_table_program(&p));
+    PoseidonTableProgram out;
+    out.instrs.assign(p.instrs, p.instrs + p.num_instrs);
+    out.immediates.assign(p.immediates, p.immediates + p.num_immediates);
+    out.num_constraints = p.num_gate_constraints;
+    gl_gate_programs_free(&p);
+    return out;
+}
+
 // gl_stark_split_program: the unit programs gl_stark_compile_units cuts desc's program into (device-free). Every unit is a
 // program of its own over desc's immediates; its EMITs are numbers emit_start .. emit_end - 1 of the program's.
 struct StarkProgramUnit {

@@ -159,6 +159,7 @@ GL_KECCAK_TABLE_COLUMNS = 2430
 GL_LOGIC_TABLE_COLUMNS, GL_LOGIC_TABLE_OP_WORDS, GL_LOGIC_TABLE_SCRATCH_BYTES = 523, 17, 16
 GL_KECCAK_SPONGE_TABLE_COLUMNS, GL_KECCAK_SPONGE_TABLE_OP_WORDS = 414, 5
 GL_ARITHMETIC_TABLE_COLUMNS, GL_ARITHMETIC_TABLE_OP_WORDS = 92, 25
+GL_POSEIDON_TABLE_COLUMNS, GL_POSEIDON_TABLE_OP_WORDS, GL_POSEIDON_TABLE_SCRATCH_BYTES, GL_POSEIDON_TABLE_MAX_DEGREE_BITS = 249, 13, 16, 23
 GL_CHALLENGER_RESET, GL_CHALLENGER_HASH, GL_CHALLENGER_COMPACT = 1, 2, 4
 GL_PROVE_STAGES = 11
 GL_STARK_STAGES = 11
@@ -291,6 +292,9 @@ SIGNATURES = {
     "gl_arithmetic_table_trace": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, ctypes.POINTER(_u64), _vp]),
     "gl_arithmetic_table_program": (GlError, [_vp]),
     "gl_debug_arithmetic_table_stage_ms": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "gl_poseidon_table_trace": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, _vp]),
+    "gl_poseidon_table_program": (GlError, [_vp]),
+    "gl_debug_poseidon_table_stage_ms": (GlError, [_vp, _u64, _u32, _vp, _u64, _vp, _u32, _vp, _vp]),
     "gl_compute_quotient_polys": (GlError, [ctypes.POINTER(GlQuotientArgs), _vp, _vp]),
     "gl_eval_polys_ext2": (GlError, [_vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "gl_fri_reduce_polys_base": (GlError, [_vp, _u32, _u64, _vp, _vp, _vp]),

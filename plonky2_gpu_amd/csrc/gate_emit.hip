@@ -18,6 +18,7 @@
 #include "program_asm.h"
 #define POSEIDON_CONST static const
 #include "poseidon_constants.h"
+#include "poseidon_table.h"
 
 namespace {
 
@@ -797,4 +798,9 @@ extern "C" void gl_gate_programs_free(GlGatePrograms *p) {
     free(p->gates);
     free(p->immediates);
     memset(p, 0, sizeof *p);
+}
+
+// poseidon_table.h: this file's host copy of the Poseidon tables for the Poseidon table's program (poseidon_table.hip)
+plonky2_hip::PoseidonHostConstants plonky2_hip::poseidon_host_constants() {
+    return PoseidonHostConstants{POSEIDON_ALL_ROUND_CONSTANTS, POSEIDON_MDS_CIRC, POSEIDON_MDS_DIAG};
 }
