@@ -1,6 +1,6 @@
 """accel.py — lets the proof-level restatements (prove_ref / fri_ref / plonk_ref, pure Python big ints) reach
-2^10..2^14 rows: inside `with c_backend():` the four primitives they spend 97 % of their time in — the Poseidon
-permutation and sponge, the Merkle tree, and the NTT — are served by the C restatement (oracle/gl_oracle.c through
+2^10..2^14 rows: inside `with c_backend():` the primitives they spend 97 % of their time in — the Poseidon
+permutation and sponge, the Merkle tree, the NTT, and the proof-of-work search — are served by the C restatement (oracle/gl_oracle.c through
 oracle.py), which is pinned by the reference's own known answers (tests/test_oracle_*.py) and by the independent model in
 pyref.py. Everything else (permutation argument, gates, quotient, challenger logic, FRI folding, openings, verifier)
 stays the Python restatement. TEST INFRASTRUCTURE ONLY.
@@ -34,6 +34,10 @@ def _two_to_one(l, r):
     return _ints(o.canon(o.two_to_one([x % P for x in l], [x % P for x in r])))
 
 
+def _pow_search(state, pos, min_leading_zeros):
+    return o.pow_search([x % P for x in state], pos, min_leading_zeros, 0, P)
+
+
 def _fast_ntt(a, inverse=False):
     v = np.array([x % P for x in a], dtype=np.uint64)
     if len(a) == 1:
@@ -55,8 +59,8 @@ pyref_hash_no_pad = pyref.hash_no_pad
 
 @contextlib.contextmanager
 def c_backend():
-    saved = {k: getattr(pyref, k) for k in ("poseidon", "hash_no_pad", "two_to_one", "fast_ntt", "merkle_tree")}
-    pyref.poseidon, pyref.hash_no_pad, pyref.two_to_one = _poseidon, _hash_no_pad, _two_to_one
+    saved = {k: getattr(pyref, k) for k in ("poseidon", "hash_no_pad", "two_to_one", "fast_ntt", "merkle_tree", "pow_search")}
+    pyref.poseidon, pyref.hash_no_pad, pyref.two_to_one, pyref.pow_search = _poseidon, _hash_no_pad, _two_to_one, _pow_search
     pyref.fast_ntt, pyref.merkle_tree = _fast_ntt, _merkle_tree
     try:
         yield

@@ -169,14 +169,7 @@ def fri_proof_of_work(challenger, params):
     pos = len(challenger.input_buffer)
     for i, x in enumerate(challenger.input_buffer):
         state[i] = x
-    cand = 0
-    while True:
-        s = list(state)
-        s[pos] = cand
-        resp = pyref.poseidon(s)[SPONGE_RATE - 1]
-        if 64 - resp.bit_length() >= min_lz:
-            break
-        cand += 1
+    cand = pyref.pow_search(state, pos, min_lz)  # accel.c_backend(): the C search, for witnesses in the millions
     challenger.observe_element(cand)
     resp = challenger.get_challenge()
     assert 64 - resp.bit_length() >= min_lz

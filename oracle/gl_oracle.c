@@ -639,6 +639,36 @@ void glo_two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]) {
     memcpy(out, st, 32);
 }
 
+/* fri_proof_of_work's predicate (fri/prover.rs:137-160): the candidate goes into the duplex state at `pos`, one permutation,
+ * and the response is the last word of the rate, as a canonical u64. [lo, hi) is scanned in slices in rising order, each slice
+ * by all the threads, so the first slice that holds a qualifying candidate holds the smallest one. */
+int glo_pow_search(const uint64_t state[12], unsigned pos, unsigned min_leading_zeros, uint64_t lo, uint64_t hi, uint64_t *witness,
+                   int n_threads) {
+    if (pos >= W) return 0;
+    const int nt = n_threads > 0 ? n_threads : 1;
+    const uint64_t slice = (uint64_t)nt << 14;
+    for (uint64_t base = lo; base < hi;) {
+        const uint64_t count = hi - base < slice ? hi - base : slice;
+        uint64_t best = UINT64_MAX;
+#pragma omp parallel for schedule(static) num_threads(nt) reduction(min : best)
+        for (uint64_t g = 0; g < count; g++) {
+            uint64_t st[W];
+            memcpy(st, state, sizeof(st));
+            st[pos] = base + g;
+            glo_poseidon(st);
+            const uint64_t resp = glo_canon(st[7]);
+            const unsigned lz = resp ? (unsigned)__builtin_clzll(resp) : 64u;
+            if (lz >= min_leading_zeros && base + g < best) best = base + g;
+        }
+        if (best != UINT64_MAX) {
+            *witness = best;
+            return 1;
+        }
+        base += count;
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ Merkle tree */
 
 /* merkle_tree.rs:78-105: layout = left subtree || left digest || right digest || right subtree.

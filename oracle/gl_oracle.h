@@ -79,6 +79,11 @@ void glo_poseidon_naive(uint64_t state[12]);  /* poseidon.rs:631-640 */
 void glo_hash_no_pad(const uint64_t *in, size_t len, uint64_t out[4]);  /* hashing.rs:81-108 */
 void glo_hash_or_noop(const uint64_t *in, size_t len, uint64_t out[4]); /* plonk/config.rs:56-67 */
 void glo_two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]); /* hashing.rs:65-72 */
+/* the proof-of-work search (fri/prover.rs:122-171): the smallest c in [lo, hi) for which glo_poseidon(state with state[pos] = c)[7],
+ * as a canonical u64, has at least min_leading_zeros leading zeros. Returns 1 and writes *witness, or 0 when the range holds none
+ * (or pos >= 12). The state is used as given: any u64 is a legal representative. */
+int glo_pow_search(const uint64_t state[12], unsigned pos, unsigned min_leading_zeros, uint64_t lo, uint64_t hi, uint64_t *witness,
+                   int n_threads);
 
 /* ---- Merkle tree (plonky2/src/hash/merkle_tree.rs) ---- */
 /* leaves: leaf-major [n_leaves][leaf_len]. digests: 4*2*(n_leaves - 2^cap_height) u64 in the

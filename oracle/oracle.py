@@ -62,6 +62,7 @@ def lib():
             ("glo_hash_no_pad", None, [_u64p, sz, _u64p]),
             ("glo_hash_or_noop", None, [_u64p, sz, _u64p]),
             ("glo_two_to_one", None, [_u64p, _u64p, _u64p]),
+            ("glo_pow_search", i, [_u64p, ui, ui, u64, u64, _u64p, i]),
             ("glo_merkle_tree", i, [_u64p, sz, sz, ui, _u64p, _u64p, i]),
             ("glo_merkle_prove", ui, [_u64p, sz, ui, sz, _u64p]),
             ("glo_merkle_verify", i, [_u64p, sz, sz, _u64p, _u64p, ui]),
@@ -182,6 +183,16 @@ def two_to_one(l, r):
     out = np.empty(4, dtype=np.uint64)
     lib().glo_two_to_one(_p(l), _p(r), _p(out))
     return out
+
+
+def pow_search(state, pos, min_leading_zeros, lo, hi, threads=None):
+    """The smallest c in [lo, hi) whose response poseidon(state with state[pos] = c)[7], canonical, has at least min_leading_zeros
+    leading zeros, or None when the range holds none (fri/prover.rs:122-171)."""
+    s = _arr(state)
+    assert s.size == 12 and 0 <= pos < 12 and 0 <= lo <= hi < 1 << 64
+    w = np.zeros(1, dtype=np.uint64)
+    found = lib().glo_pow_search(_p(s), pos, min_leading_zeros, lo, hi, _p(w), threads or min(usable_threads(), 16))
+    return int(w[0]) if found else None
 
 
 def merkle_tree(leaves, cap_height, threads=1):

@@ -153,6 +153,18 @@ def poseidon(state):
     return s
 
 
+def pow_search(state, pos, min_leading_zeros):
+    """The smallest candidate c for which poseidon(state with state[pos] = c)[7] has at least min_leading_zeros leading zeros as a
+    64-bit word: the search of fri_proof_of_work (fri/prover.rs:122-171), one permutation at a time."""
+    s = list(state)
+    cand = 0
+    while True:
+        s[pos] = cand
+        if 64 - poseidon(s)[7].bit_length() >= min_leading_zeros:
+            return cand
+        cand += 1
+
+
 def hash_no_pad(inputs):
     """hash_n_to_hash_no_pad (plonky2/src/hash/hashing.rs:81-108): overwrite-mode sponge, rate 8."""
     st = [0] * WIDTH

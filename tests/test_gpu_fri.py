@@ -337,3 +337,189 @@ def test_device_transcript_entry_points_refuse_bad_arguments(gpu):
     gpu.synchronize()
     assert not d.download()[:12].any() and int(d.download()[28]) == 0   # the reset left an empty transcript
     d.free()
+
+
+# ---- proof of work beyond the first batch of the search ----------------------------------------------------------------------
+# fri_proof_of_work scans 2^17 candidates, then 2^18, .. doubling to 2^24 and staying there, clearing `best` before every launch.
+# The rows of tests/golden/pow_witnesses.json are smallest witnesses (proven by the fixture's generator, re-checked on the CPU by
+# tests/test_pow_fixture.py) in batches 2, 3, 4, 5, the first capped batch and a later capped one.
+
+def _pow_rows():
+    import pow_instance as pi
+
+    return pi.load()
+
+
+def _host_pow(gpu, state, pos, min_lz):
+    import ctypes
+
+    from plonky2_gpu_amd import _lib
+
+    w = ctypes.c_uint64(0xDEADBEEF)
+    _lib.call("gl_fri_proof_of_work", np.array(state, dtype=np.uint64), pos, min_lz, ctypes.addressof(w), gpu.ptr)
+    return w.value
+
+
+class _DeviceTranscript:
+    """A transcript as pow_kernel reads it: T[0..12) the sponge state, T[12..20) the pending inputs, T[28] their count. The pending
+    inputs overwrite the first `pos` state words, the candidate goes behind them: `state` is the duplex state after that overwrite,
+    so its first `pos` words go into the input buffer and something else stands where they will be written."""
+
+    def __init__(self, gpu):
+        import plonky2_gpu_amd as pg
+
+        self.gpu, self.d_t, self.d_w = gpu, pg.DeviceBuffer(gpu, 32), pg.DeviceBuffer(gpu, 2)
+
+    def search(self, state, pos, min_lz):
+        """(witness returned to the host, witness left in d_witness)"""
+        import ctypes
+
+        from plonky2_gpu_amd import _lib
+
+        T = np.zeros(32, dtype=np.uint64)
+        T[:12] = state
+        T[:pos] = [0x5EED0000 + k for k in range(pos)]  # overwritten by the pending inputs
+        T[12 : 12 + pos] = state[:pos]
+        T[12 + pos : 20] = 0x0BAD0BAD  # behind the count: not inputs
+        T[28] = pos
+        self.d_t.upload(T)
+        w = ctypes.c_uint64(0xDEADBEEF)
+        _lib.call("gl_fri_proof_of_work_device", self.d_t.ptr, min_lz, self.d_w.ptr, ctypes.byref(w), self.gpu.ptr)
+        assert (self.d_t.download() == T).all()  # the search reads the transcript, observing the witness is the caller's step
+        return w.value, int(self.d_w.download()[0])
+
+    def free(self):
+        self.d_t.free()
+        self.d_w.free()
+
+
+@pytest.mark.parametrize("k", range(6))
+def test_proof_of_work_finds_the_smallest_witness_beyond_the_first_batch(gpu, k):
+    import pow_instance as pi
+
+    row = _pow_rows()[k]
+    assert row["batch"] >= 2 and row["witness"] >= pi.FIRST_BATCH
+    state, min_lz = pi.state(row["seed"]), pi.min_leading_zeros(row["bits"])
+    print("seed %d, %d bits: witness %d in batch %d" % (row["seed"], row["bits"], row["witness"], row["batch"]))
+    assert _host_pow(gpu, state, pi.POS, min_lz) == row["witness"]
+    dt = _DeviceTranscript(gpu)
+    try:
+        assert dt.search(state, pi.POS, min_lz) == (row["witness"], row["witness"])
+    finally:
+        dt.free()
+
+
+@pytest.mark.parametrize("pos,seed", [(0, 101), (7, 100)])
+def test_device_proof_of_work_at_other_witness_positions(gpu, pos, seed):
+    """no pending input (the candidate is the first word) and seven of them (it is the last word of the rate), 18 bits, witnesses
+    beyond the first batch by the C search; position 3 is the fixture's"""
+    import pow_instance as pi
+    from oracle import oracle as o
+
+    state, min_lz = pi.state(seed), pi.min_leading_zeros(18)
+    want = o.pow_search(state, pos, min_lz, 0, P)
+    assert want >= pi.FIRST_BATCH  # a property of the instance, asserted on the reference
+    dt = _DeviceTranscript(gpu)
+    try:
+        assert dt.search(state, pos, min_lz) == (want, want)
+    finally:
+        dt.free()
+    assert _host_pow(gpu, state, pos, min_lz) == want
+
+
+def test_proof_of_work_leaves_nothing_behind_for_the_next_search(gpu):
+    """`best` is scratch that every search reuses (the context's for the host entry point, d_witness for the device one): a long
+    search right after a short one and a short one right after a long one, on one context and one d_witness, both ways round"""
+    import pow_instance as pi
+    from oracle import oracle as o
+
+    rows = _pow_rows()
+    far = rows[3]  # batch 5
+    near_state = pi.state(100)
+    near = o.pow_search(near_state, pi.POS, 6, 0, P)
+    assert near < 1000 < pi.FIRST_BATCH <= far["witness"]
+    far_state, far_lz = pi.state(far["seed"]), pi.min_leading_zeros(far["bits"])
+    dt = _DeviceTranscript(gpu)
+    try:
+        for _ in range(2):
+            assert _host_pow(gpu, near_state, pi.POS, 6) == near
+            assert _host_pow(gpu, far_state, pi.POS, far_lz) == far["witness"]
+            assert dt.search(near_state, pi.POS, 6) == (near, near)
+            assert dt.search(far_state, pi.POS, far_lz) == (far["witness"], far["witness"])
+        assert _host_pow(gpu, near_state, pi.POS, 6) == near
+    finally:
+        dt.free()
+
+
+def test_proof_of_work_at_the_edges_of_the_predicate(gpu):
+    import pow_instance as pi
+    from oracle import oracle as o
+
+    rows = _pow_rows()
+    dt = _DeviceTranscript(gpu)
+    try:
+        # no leading zero asked for: every response qualifies, the smallest candidate is 0
+        assert _host_pow(gpu, pi.state(100), pi.POS, 0) == 0
+        assert dt.search(pi.state(100), pi.POS, 0) == (0, 0)
+        # a state word >= p: the host entry point reduces it, the witness is the canonical state's
+        row = rows[1]
+        lifted = pi.state(row["seed"])
+        lifted[5] += P
+        lifted[11] += P
+        assert all(lifted[k] < 1 << 64 for k in (5, 11))
+        assert _host_pow(gpu, lifted, pi.POS, pi.min_leading_zeros(row["bits"])) == row["witness"]
+        # the witness's neighbours at p - 1
+        state = pi.state(100)
+        state[pi.POS - 1] = state[pi.POS + 1] = P - 1
+        want = o.pow_search(state, pi.POS, 18, 0, P)
+        assert want >= pi.FIRST_BATCH
+        assert _host_pow(gpu, state, pi.POS, 18) == want
+        assert dt.search(state, pi.POS, 18) == (want, want)
+    finally:
+        dt.free()
+
+
+def test_a_plonk_proof_whose_proof_of_work_witness_lies_beyond_the_first_batch(gpu):
+    """the smallest circuit of plonk_instance.make_circuit at 18 proof-of-work bits; seed 1 is the first whose witness is >= 2^17
+    (about six seeds in ten are), which is asserted on the reference prover's witness"""
+    import plonky2_gpu_amd as pg
+    import pow_instance as pi
+    from oracle import accel, prove_ref, serialize_ref
+    from plonk_instance import make_circuit
+
+    with accel.c_backend():
+        circuit, wires, pis = make_circuit(3, seed=1, arity_bits=(1,), cap_height=0, pow_bits=18, num_queries=1)
+        ref = prove_ref.prove(circuit, wires, pis)
+    witness = ref["opening_proof"]["pow_witness"]
+    assert witness >= pi.FIRST_BATCH and pi.batch_of(witness)[0] >= 2
+    nc = pg.NativeCircuit(gpu, dict(circuit, circuit_digest=None))
+    try:
+        data = nc.prove_bytes(wires, pis)
+    finally:
+        nc.close()
+    assert pg.serialization.proof_from_bytes(data, circuit)["opening_proof"]["pow_witness"] == witness
+    assert data == serialize_ref.proof_bytes(ref)
+
+
+def test_a_stark_proof_whose_proof_of_work_witness_lies_beyond_the_first_batch(gpu):
+    """the smallest STARK of stark_instances (A on two rows) at 18 proof-of-work bits; seed 1 is the first whose witness is >= 2^17"""
+    import generic_prove_ref as gr
+    import plonky2_gpu_amd as pg
+    import pow_instance as pi
+    import stark_instances as si
+    import stark_ref as sr
+    from oracle import accel
+
+    hasher = gr.PoseidonHasher()
+    fp = si.fri_params(rate_bits=1, cap_height=0, arity_bits=(), num_query_rounds=1, proof_of_work_bits=18)
+    trace, pis = si.A.make_trace(1, seed=1)
+    with accel.c_backend():
+        ref = sr.prove(hasher, si.A, 1, fp, trace, pis)
+    witness = ref["opening_proof"]["pow_witness"]
+    assert witness >= pi.FIRST_BATCH and pi.batch_of(witness)[0] >= 2
+    ns = pg.NativeStark(gpu, si.A.desc(1, 1, fp), "poseidon")
+    try:
+        data = ns.prove_bytes(trace, pis)
+    finally:
+        ns.close()
+    assert data == sr.proof_bytes(hasher, ref)
